@@ -19,6 +19,13 @@ device in the untimed setup ("1M images projected with config-2 W")
 --w random keeps the round-1..4 random N(0, 1/D) W.  Gallery/queries are synthetic
 (see opencv_facerecognizer_amd/synthetic.py).
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline needs and no more: setup,
+warm-up, the N timed steps, --dump-outputs if given, the result line (its per-kernel times are the timed
+steps' own events).  --full adds everything else the benchmark measures: the CPU baseline, configs[4]
+(the W trained through PredictableModel.compute, timed -- the same W) and the API's predict_batch,
+configs[1], configs[3], the small-batch and stress runs, and the figures that take runs of their own
+(preparation and merge alone, certificate margin, feature profile).
+
 Multi-GPU (torch.distributed.run, one process per GPU): the 1M gallery is
 sharded by rows over the ranks; each rank projects and quantizes B/G of the
 query faces and the centred fp32 rows + fp6 panels are all-gathered (RCCL), every
@@ -69,6 +76,15 @@ def parse():
     ap.add_argument("--dim", type=int, default=9999)
     ap.add_argument("--side", type=int, default=100)
     ap.add_argument("--k", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (and a seeded sample of its "
+                         "projected query rows) as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, configs[4] training through the API and the API's "
+                         "predict_batch, configs[1], configs[3], the small-batch and stress runs, and the figures "
+                         "that take runs of their own (preparation and merge alone, certificate margin, feature "
+                         "profile).  Without it a run sets up, warms up, times --steps steps and prints the result "
+                         "line; the options below that select those extras only apply with --full")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--small-batches", default="32,1", help="extra HBM-regime measurements (B <= 32); '' to skip")
@@ -90,7 +106,13 @@ def parse():
     ap.add_argument("--search", choices=["f6", "q8", "fp32"], default="f6",
                     help="f6: certified fp6 coarse pass (uncertified queries go down the int8 tiers, then fp32); "
                          "q8: start at the certified int8 tier; fp32: fp32-MFMA pass")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # the plain run: the headline figure only (the W comes from the untimed device training pipeline,
+        # the same fisherfaces_device call on the same faces as configs[4]'s PredictableModel.compute)
+        args.no_cpu, args.small_batches, args.stress = True, "", ""
+        args.config1 = args.config3 = args.config4 = args.api = 0
+    return args
 
 
 def log(rank, *a):
@@ -623,6 +645,35 @@ def stress_run(P, bank, args, noise, device, N=None):
     return res
 
 
+DUMP_BUDGET = 64 * 1000 * 1000   # bytes of .npy data a --dump-outputs run writes at most
+
+
+def dump_outputs(path, res, Qd, d):
+    """--dump-outputs: what the last timed step handed its caller, as path/<name>.npy -- distances (float64
+    [B][k], the exact re-ranked distances) and indices (the gallery rows, as float64: exact below 2^53) --
+    and query_features (float32 [S][d]), the centred projections W^T x - c the step searched with, for the S
+    rows listed in query_feature_rows.  The rows are a sample drawn from SEED (all of them where they fit), the
+    same for every run with the same arguments, as are the inputs: two builds compare output for output."""
+    os.makedirs(path, exist_ok=True)
+    dist_, idx = res[0].detach().cpu().numpy(), res[1].detach().cpu().numpy()
+    B, k = dist_.shape
+    rng = np.random.default_rng(SEED)
+
+    def sample(row_bytes, budget):
+        n = min(B, max(1, budget // row_bytes))
+        return np.arange(B) if n == B else np.sort(rng.choice(B, n, replace=False))
+
+    rows = sample(16 * k + 8, DUMP_BUDGET // 4)
+    if len(rows) < B:
+        np.save(os.path.join(path, "result_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "distances.npy"), dist_[rows].astype(np.float64))
+    np.save(os.path.join(path, "indices.npy"), idx[rows].astype(np.float64))
+    frows = sample(4 * d + 8, min(DUMP_BUDGET // 2, 512 * (4 * d + 8)))
+    sel = torch.from_numpy(frows).to(Qd.device)
+    np.save(os.path.join(path, "query_features.npy"), Qd.index_select(0, sel)[:, :d].float().cpu().numpy())
+    np.save(os.path.join(path, "query_feature_rows.npy"), frows.astype(np.float64))
+
+
 def launch_ranks(n, cmd=None, poll_s=0.2):
     """`bench.py --gpus N` without a launcher: start N rank processes of this script (RANK, LOCAL_RANK,
     WORLD_SIZE, MASTER_ADDR=127.0.0.1, a free MASTER_PORT) and wait for them.  Runs before anything
@@ -835,16 +886,19 @@ def main():
         elapsed = float(t.item())
     last = (args.steps - 1) % StepPipeline.NBUF
     Qd, qq = bufs[last]["Qd"], bufs[last]["qq"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, Qd, d)
 
-    ms_proj = np.mean([e[0].elapsed_time(e[1]) for e in ev])
+    ms_proj =np.mean([e[0].elapsed_time(e[1]) for e in ev])
     ms_tiles = np.mean([e[4].elapsed_time(e[2]) for e in ev])     # the tile pass on the main stream
     ms_sample = np.mean([e[4].elapsed_time(e[6]) for e in ev])    # its sample pass + thresholds
     ms_sieve = np.mean([e[6].elapsed_time(e[2]) for e in ev])     # its sieve pass (fp6; else the rest)
     ms_merge = np.mean([e[5].elapsed_time(e[3]) for e in ev])     # merge + certificate on the side stream
     # the preparation alone (the last batch's projection + quantization again, same outputs): with merge_at
     # "tail" the step's preparation events also span the merge run beside the projection's last round
+    # (runs of its own: --full; a plain run reports the step's events)
     ms_proj_alone = None
-    if not shard_prep and world == 1:
+    if args.full and not shard_prep and world == 1:
         xs, tq = Xqs[last], bufs[last].get("tier", tier0)
         ms_pa = []
         for _ in range(5):
@@ -924,7 +978,7 @@ def main():
     # the merge alone (phase 2 of the last batch again on its workspace: idempotent), and its bytes: the fp32
     # rows of the candidates it re-ranked exactly (MergeArgs::evals), the query rows, the kept bucket entries
     merge_roof = None
-    if args.search == "f6" and world == 1:
+    if args.full and args.search == "f6" and world == 1:
         wl = pipe.ws[(args.steps - 1) % StepPipeline.NWS]
         ms_m = []
         for _ in range(5):
@@ -946,7 +1000,7 @@ def main():
                           "exact_reranks_per_query": n_ev / B, "algorithmic_bytes": mb,
                           "achieved": mb / (mm * 1e-3) / 1e9, "peak": PEAK_HBM / 1e9, "unit": "GB/s",
                           "frac": mb / (mm * 1e-3) / PEAK_HBM}
-    margin = certificate_margin(gallery, Qd, qq) if args.search == "f6" and world == 1 else None
+    margin = certificate_margin(gallery, Qd, qq) if args.full and args.search == "f6" and world == 1 else None
     flops_tiles = 2.0 * B * nl * d                                    # algorithmic, per launch
     achieved = flops_tiles / (ms_tiles * 1e-3)
     # the tier the timed steps started at (FloatGallery.start_tier): f6p (the prefix tier) when the
@@ -1066,7 +1120,7 @@ def main():
             "projection_w": w_info,
             "config4": c4,
             "api": api,
-            "feature_profile": feature_profile(gallery) if args.search == "f6" else None,
+            "feature_profile": feature_profile(gallery) if args.full and args.search == "f6" else None,
             "small_batch": small,
         }
         if world == 1 and not args.no_cpu:

@@ -12,7 +12,7 @@ rc=$?
 tail -5 gpurun_out/${TAG}_gpu_tests.txt
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "tests rc=$rc: stopping"; exit $rc; fi
 if [ "${BENCH:-1}" = "1" ]; then
-  timeout -k 10 ${BENCH_TIMEOUT:-400} python -u bench.py ${BENCH_ARGS:---steps 10 --warmup 2} \
+  timeout -k 10 ${BENCH_TIMEOUT:-400} python -u bench.py ${BENCH_ARGS:---full --steps 10 --warmup 2} \
       > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.log
   brc=$?
   tail -3 gpurun_out/${TAG}_bench.log; cut -c1-600 gpurun_out/${TAG}_bench.json
