@@ -46,6 +46,11 @@ enum ofr_metric {
   OFR_METRIC_EUCLIDEAN = 0, /* distance.py:53-60  sqrt(sum((p-q)^2))            */
   OFR_METRIC_COSINE = 1,    /* distance.py:63-77  -p.q / sqrt((p.p)(q.q))        */
   OFR_METRIC_CHISQUARE = 2, /* distance.py:101-116 sum((p-q)^2/(p+q+eps))        */
+  /* histogram metrics (ofr_hist_knn, ofr_knn_deep); a = |1 - p.q|, eps as above */
+  OFR_METRIC_HISTINTERSECT = 3, /* distance.py:119-126 sum(min(p,q)), ascending like the rest */
+  OFR_METRIC_BINRATIO = 4,      /* :129-145 |sum(((p-q)^2 + 2a pq) / ((p+q)^2+eps))|          */
+  OFR_METRIC_L1BINRATIO = 5,    /* :148-164 the same, numerator times |p-q|                   */
+  OFR_METRIC_CHISQBRD = 6,      /* :167-183 numerator times (p-q)^2, denominator (p+q)^3+eps  */
 };
 
 enum ofr_dtype { OFR_DT_U8 = 0, OFR_DT_U16 = 1, OFR_DT_U32 = 2, OFR_DT_F32 = 3, OFR_DT_F64 = 4 };
@@ -371,7 +376,8 @@ int ofr_knn_f6x2(void* stream, int phases, const float* Q, int64_t B, int64_t ld
 /* Any k (round 5; replaces NearestNeighbor.predict classifier.py:104-119 for the k the tiers
  * above do not serve -- they keep 16 candidates per tile): the reference's distance of every
  * (query, row) pair in fp64 (Euclidean distance.py:57-60, Cosine :74-77 with NaN for a zero row,
- * ChiSquare :112-116), then per query the k smallest by (distance, row), NaN last.  Q [B][ldq] of
+ * ChiSquare :112-116, the four histogram metrics :119-183 as T1 + 2 |1 - p.q| T2 with the three
+ * sums kept per pair), then per query the k smallest by (distance, row), NaN last.  Q [B][ldq] of
  * qdtype, G [N][ldg] of gdtype (OFR_DT_*; integer rows are counts, value = count / denom as the
  * reference's float64 histograms; denom 1 for float rows).  out_d / out_i [B][k]; entries past
  * min(k, N) are (+inf, -1).  Any k: min(k, N) <= 4096 by a radix select in LDS, above it by a
@@ -442,6 +448,25 @@ int ofr_chi2_knn(void* stream, int dtype, const void* Q, int64_t B, int64_t ldq,
 int ofr_chi2_knn_exact(void* stream, int dtype, const void* Q, int64_t B, int64_t ldq, const void* G, int64_t N,
                        int64_t ldg, int64_t nbins, double denom, int k, int64_t index_base, double* out_d,
                        int64_t* out_i, void* workspace, size_t workspace_bytes, int* cert);
+
+/* Histogram-intersection and bin-ratio search --------------------------------
+ * Replaces HistogramIntersection, BinRatioDistance, L1BinRatioDistance and ChiSquareBRD
+ * (distance.py:119-183) inside NearestNeighbor.predict; metric = OFR_METRIC_HISTINTERSECT ..
+ * OFR_METRIC_CHISQBRD.  Arguments, alignment, outputs and the k <= OFR_MAX_K limit as ofr_chi2_knn;
+ * rows are histograms (non-negative).  Every metric sorts ascending, ties to the lower row: under
+ * HistogramIntersection the first row returned has the SMALLEST overlap, as in the reference.
+ * Coarse pass per element type: intersection of uint8 / uint16 counts by v_sad_u8 / v_sad_u16 on
+ * the packed counts (integer scores: exact, cert = 1 while the query's total count is < 2^24);
+ * bin-ratio forms of uint8 counts by v_dot4_u32_u8 for p.q plus fp32 sums; everything else in fp32
+ * with an fp64 dot product.  The best 16 rows per tile are re-evaluated with the reference formula
+ * in fp64; cert as ofr_chi2_knn with gamma = (nbins + 20) 2^-24 (the bin-ratio forms never certify
+ * a query whose row, or whose candidate tiles, hold a uint32 count >= 2^24: fp32 rounds those).
+ * Queries with cert 0 (and k >
+ * OFR_MAX_K) are served by ofr_knn_deep with the same metric.                              */
+size_t ofr_hist_workspace_bytes(int64_t B, int64_t N, int k);
+int ofr_hist_knn(void* stream, int metric, int dtype, const void* Q, int64_t B, int64_t ldq, const void* G,
+                 int64_t N, int64_t ldg, int64_t nbins, double denom, int k, int64_t index_base, double* out_d,
+                 int64_t* out_i, void* workspace, size_t workspace_bytes, int* cert);
 
 /* Training (PCA Gram / LDA scatter) ----------------------------------------
  * C[M][N] = alpha * op(A) op(B) + beta * C in fp64 on the fp64 MFMA

@@ -1042,11 +1042,16 @@ def infer_count_denom(F):
 
 
 class Chi2Gallery:
-    """Device gallery for ChiSquare search: fp32 values, or integer counts with a denominator
-    (the LBP spatial histograms: count / cell, held as the counts -- exact and 4x smaller)."""
+    """Device gallery of histogram rows for the ChiSquare search and, with `metric` one of the other
+    _lib.HIST_METRICS, the histogram-intersection / bin-ratio searches: fp32 values, or integer counts
+    with a denominator (the LBP spatial histograms: count / cell, held as the counts -- exact and 4x
+    smaller)."""
 
-    def __init__(self, rows, dtype=_lib.DT_F32, denom=1.0, nbins=None, device=None):
+    def __init__(self, rows, dtype=_lib.DT_F32, denom=1.0, nbins=None, device=None, metric=_lib.METRIC_CHISQUARE):
         device = device or dev()
+        if metric not in _lib.HIST_METRICS:
+            raise ValueError(f"metric {metric} is not a histogram metric")
+        self.metric = metric
         self.dtype = dtype
         self.denom = float(denom)
         if isinstance(rows, torch.Tensor):
@@ -1062,7 +1067,7 @@ class Chi2Gallery:
         self.last_fallbacks = ()
 
     @classmethod
-    def from_counts(cls, C, count_bytes, denom, device=None):
+    def from_counts(cls, C, count_bytes, denom, device=None, metric=_lib.METRIC_CHISQUARE):
         """Host or device counts [n][nbins] (uint8 / uint16 / uint32 values) -> a counts gallery."""
         dt, tdt, ndt, _ = _COUNT_DT[count_bytes]
         device = device or dev()
@@ -1076,7 +1081,7 @@ class Chi2Gallery:
             Gp = torch.zeros((G.shape[0], ld), dtype=tdt, device=device)
             Gp[:, :nbins] = G
             G = Gp
-        return cls(G, dtype=dt, denom=denom, nbins=nbins, device=device)
+        return cls(G, dtype=dt, denom=denom, nbins=nbins, device=device, metric=metric)
 
     @property
     def count_bytes(self):
@@ -1126,6 +1131,8 @@ class Chi2Gallery:
         = (uncertified after the fp32 pass, uncertified after the exact pass: near-ties at fp32 key
         resolution, 2^-23 relative).  k > 16: the exact any-k pass (search_deep)."""
         B = Qd.shape[0]
+        if self.metric != _lib.METRIC_CHISQUARE:
+            return self._search_hist(Qd, k, index_base)
         if k > _lib.MAX_K:
             self.last_fallbacks = (0,)
             return search_deep(_lib.METRIC_CHISQUARE, Qd, self.dtype, self.G, self.dtype, self.nbins, self.denom, k,
@@ -1153,6 +1160,34 @@ class Chi2Gallery:
             out_i.index_copy_(0, rows, i2)
             counts.append(int((c2 == 0).sum()))
         self.last_fallbacks = tuple(counts)
+        return out_d, out_i
+
+    def _search_hist(self, Qd, k, index_base=0):
+        """Histogram intersection / bin-ratio top-k (ofr_hist_knn): a coarse tile pass (integer SADs for
+        the intersection of uint8 / uint16 counts, exact by construction; fp32 sums with an exact or
+        fp64 dot product otherwise), the fp64 re-rank and its certificate.  Queries it cannot certify,
+        and every k > 16, take the exact fp64 any-k pass (search_deep).  self.last_fallbacks =
+        (queries re-run exactly,)."""
+        B = Qd.shape[0]
+        if k > _lib.MAX_K:
+            self.last_fallbacks = (0,)
+            return search_deep(self.metric, Qd, self.dtype, self.G, self.dtype, self.nbins, self.denom, k,
+                               index_base, workspace=self.ws)
+        out_d = torch.empty((B, k), dtype=torch.float64, device=Qd.device)
+        out_i = torch.empty((B, k), dtype=torch.int64, device=Qd.device)
+        cert = torch.empty(B, dtype=torch.int32, device=Qd.device)
+        ws = self.ws.get(_lib.load().ofr_hist_workspace_bytes(B, self.N, k), Qd.device)
+        call("ofr_hist_knn", stream(), self.metric, self.dtype, ptr(Qd), B, Qd.shape[1], ptr(self.G), self.N,
+             self.G.shape[1], self.nbins, self.denom, k, index_base, ptr(out_d), ptr(out_i), ptr(ws), ws.numel(),
+             ptr(cert))
+        rows = open_rows(cert)
+        if rows.numel():
+            sub = Qd.index_select(0, rows).contiguous()
+            d2, i2 = search_deep(self.metric, sub, self.dtype, self.G, self.dtype, self.nbins, self.denom, k,
+                                 index_base, workspace=self.ws)
+            out_d.index_copy_(0, rows, d2)
+            out_i.index_copy_(0, rows, i2)
+        self.last_fallbacks = (int(rows.numel()),)
         return out_d, out_i
 
     def query_rows(self, arr):

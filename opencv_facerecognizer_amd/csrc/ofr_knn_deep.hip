@@ -7,7 +7,9 @@
 //   deep_dist_kernel   the reference's distance of every (query, row) pair in fp64 -- Euclidean
 //                      sqrt(sum (p - q)^2) (distance.py:57-60), Cosine -p.q / sqrt(p.p q.q)
 //                      (:74-77, NaN for a zero row as numpy's 0/0), ChiSquare
-//                      sum (p - q)^2 / (p + q + eps) (:112-116) -- on 64 x 64 tiles with the
+//                      sum (p - q)^2 / (p + q + eps) (:112-116), HistogramIntersection sum min(p, q)
+//                      (:126), the bin-ratio forms (:129-183) as T1 + 2 |1 - p.q| T2 with T1, T2 and
+//                      p.q summed per pair and combined at the end -- on 64 x 64 tiles with the
 //                      features staged through LDS (fp32 rows, or count rows / denom: the
 //                      reference's float64 histogram values bit for bit);
 //   deep_select_kernel per query the k smallest (distance, row) pairs: an 8-pass radix select of
@@ -67,12 +69,15 @@ __global__ void __launch_bounds__(256) deep_dist_kernel(DistArgs a) {
   __shared__ double qs[KB][TQ + 1], gs[KB][TG + 1];
   const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
   const int64_t q0 = (int64_t)blockIdx.y * TQ, g0 = (int64_t)blockIdx.x * TG;
-  double acc[4][4], qq[4], gg[4];
+  // bin-ratio forms (distance.py:129-183): acc = T1, acc2 = T2, dotp = p.q, combined at the end
+  constexpr bool BINRATIO = METRIC == OFR_METRIC_BINRATIO || METRIC == OFR_METRIC_L1BINRATIO ||
+                            METRIC == OFR_METRIC_CHISQBRD;
+  double acc[4][4], acc2[4][4], dotp[4][4], qq[4], gg[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     qq[i] = gg[i] = 0.0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+    for (int j = 0; j < 4; ++j) acc[i][j] = acc2[i][j] = dotp[i][j] = 0.0;
   }
   for (int64_t k0 = 0; k0 < a.d; k0 += KB) {
     // stage KB features of the tile's 64 queries and 64 rows (zeros past d / B / N)
@@ -107,6 +112,15 @@ __global__ void __launch_bounds__(256) deep_dist_kernel(DistArgs a) {
             acc[i][j] = fma(df, df, acc[i][j]);
           } else if constexpr (METRIC == OFR_METRIC_COSINE) {
             acc[i][j] = fma(qv[i], gv[j], acc[i][j]);
+          } else if constexpr (METRIC == OFR_METRIC_HISTINTERSECT) {
+            acc[i][j] += fmin(qv[i], gv[j]);   // distance.py:126
+          } else if constexpr (BINRATIO) {
+            const double df = qv[i] - gv[j], s = qv[i] + gv[j], d2 = df * df;
+            const double den = (METRIC == OFR_METRIC_CHISQBRD ? s * s * s : s * s) + 2.220446049250313e-16;
+            const double w = METRIC == OFR_METRIC_BINRATIO ? 1.0 : METRIC == OFR_METRIC_L1BINRATIO ? fabs(df) : d2;
+            acc[i][j] += d2 * w / den;
+            acc2[i][j] += qv[i] * gv[j] * w / den;
+            dotp[i][j] = fma(qv[i], gv[j], dotp[i][j]);
           } else {
             const double df = qv[i] - gv[j];
             acc[i][j] += (df * df) / ((qv[i] + gv[j]) + 2.220446049250313e-16);   // distance.py:115-116
@@ -126,6 +140,7 @@ __global__ void __launch_bounds__(256) deep_dist_kernel(DistArgs a) {
       double v = acc[i][j];
       if constexpr (METRIC == OFR_METRIC_EUCLIDEAN) v = sqrt(v);
       if constexpr (METRIC == OFR_METRIC_COSINE) v = -v / sqrt(qq[i] * gg[j]);   // 0 / 0 = NaN, as numpy
+      if constexpr (BINRATIO) v = fabs(v + 2.0 * fabs(1.0 - dotp[i][j]) * acc2[i][j]);
       a.D[q * a.N + g] = v;
     }
   }
@@ -296,8 +311,7 @@ extern "C" int ofr_knn_deep(void* stream, int metric, const void* Q, int64_t B, 
                             const void* G, int64_t N, int64_t ldg, int gdtype, int64_t d, double denom, int k,
                             int64_t index_base, double* out_d, int64_t* out_i, void* workspace,
                             size_t workspace_bytes) {
-  OFR_CHECK_ARG(metric == OFR_METRIC_EUCLIDEAN || metric == OFR_METRIC_COSINE || metric == OFR_METRIC_CHISQUARE,
-                "ofr_knn_deep: unknown metric");
+  OFR_CHECK_ARG(metric >= OFR_METRIC_EUCLIDEAN && metric <= OFR_METRIC_CHISQBRD, "ofr_knn_deep: unknown metric");
   OFR_CHECK_ARG(B >= 0 && N >= 0 && d >= 1 && ldq >= d && ldg >= d && k >= 1, "ofr_knn_deep: bad sizes");
   OFR_CHECK_ARG(qdtype >= OFR_DT_U8 && qdtype <= OFR_DT_F64 && gdtype >= OFR_DT_U8 && gdtype <= OFR_DT_F64,
                 "ofr_knn_deep: bad dtype");
@@ -343,8 +357,16 @@ extern "C" int ofr_knn_deep(void* stream, int metric, const void* Q, int64_t B, 
         hipLaunchKernelGGL(deep::deep_dist_kernel<OFR_METRIC_EUCLIDEAN>, grid, dim3(256), 0, st, a);
       else if (metric == OFR_METRIC_COSINE)
         hipLaunchKernelGGL(deep::deep_dist_kernel<OFR_METRIC_COSINE>, grid, dim3(256), 0, st, a);
-      else
+      else if (metric == OFR_METRIC_CHISQUARE)
         hipLaunchKernelGGL(deep::deep_dist_kernel<OFR_METRIC_CHISQUARE>, grid, dim3(256), 0, st, a);
+      else if (metric == OFR_METRIC_HISTINTERSECT)
+        hipLaunchKernelGGL(deep::deep_dist_kernel<OFR_METRIC_HISTINTERSECT>, grid, dim3(256), 0, st, a);
+      else if (metric == OFR_METRIC_BINRATIO)
+        hipLaunchKernelGGL(deep::deep_dist_kernel<OFR_METRIC_BINRATIO>, grid, dim3(256), 0, st, a);
+      else if (metric == OFR_METRIC_L1BINRATIO)
+        hipLaunchKernelGGL(deep::deep_dist_kernel<OFR_METRIC_L1BINRATIO>, grid, dim3(256), 0, st, a);
+      else
+        hipLaunchKernelGGL(deep::deep_dist_kernel<OFR_METRIC_CHISQBRD>, grid, dim3(256), 0, st, a);
       OFR_LAUNCH_CHECK("deep_dist_kernel");
     }
     if (sorted) {

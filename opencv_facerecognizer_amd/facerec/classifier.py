@@ -139,7 +139,8 @@ class NearestNeighbor(AbstractClassifier):
         mid = getattr(self.dist_metric, "metric_id", None)
         if mid is None:
             raise NotImplementedError(
-                f"{self.dist_metric!r} has no device kernel (supported: Euclidean, Cosine, ChiSquare)")
+                f"{self.dist_metric!r} has no device kernel (supported: Euclidean, Cosine, ChiSquare, "
+                "HistogramIntersection, BinRatio, L1-BinRatio, ChiSquare-BinRatio)")
         return mid
 
     def _invalidate(self):
@@ -174,8 +175,8 @@ class NearestNeighbor(AbstractClassifier):
             raise ValueError(f"a gallery of {n} rows cannot be sharded over {ws} ranks")
         n0, n1 = shard_range(n, rank, ws)
         feats = self._stack(self.X[n0:n1])
-        if mid == _lib.METRIC_CHISQUARE:
-            g = self._chi2_gallery(feats)
+        if mid in _lib.HIST_METRICS:
+            g = self._chi2_gallery(feats, mid)
         else:
             # the same centre on every rank: the mean of all rows, from the host copy every rank holds
             shift = self._stack(self.X).mean(0) if mid == _lib.METRIC_EUCLIDEAN else None
@@ -220,26 +221,27 @@ class NearestNeighbor(AbstractClassifier):
                         self.__dict__["_dev"] = (key, n, g)
                         return g
             feats = self._stack(self.X) if n else np.zeros((0, 1))
-            g = self._chi2_gallery(feats) if mid == _lib.METRIC_CHISQUARE else FloatGallery(feats, mid)
+            g = self._chi2_gallery(feats, mid) if mid in _lib.HIST_METRICS else FloatGallery(feats, mid)
             self.__dict__["_dev"] = (key, n, g)
             return g
 
-    def _chi2_gallery(self, feats):
-        """ChiSquare gallery of host rows: the LBP spatial histograms (count / cell, feature.py:298-299)
-        are held as their integer counts (exact, a quarter of the fp32 bytes); anything else as fp32."""
+    def _chi2_gallery(self, feats, mid=_lib.METRIC_CHISQUARE):
+        """Histogram-metric gallery (ChiSquare, intersection, bin-ratio) of host rows: the LBP spatial
+        histograms (count / cell, feature.py:298-299) are held as their integer counts (exact, a quarter
+        of the fp32 bytes); anything else as fp32."""
         hint = self.__dict__.get("_chi2_denom")
         denom = hint if hint is not None else (infer_count_denom(feats) if len(feats) else None)
         got = counts_of(feats, denom) if denom else None
         if got is None:
-            return Chi2Gallery(feats)
+            return Chi2Gallery(feats, metric=mid)
         self.__dict__["_chi2_denom"] = denom
-        return Chi2Gallery.from_counts(got[0], got[1], denom)
+        return Chi2Gallery.from_counts(got[0], got[1], denom, metric=mid)
 
     def adopt_device_rows(self, F):
         """Seed the device gallery from fp64 device rows F [N][d] equal to self.X (e.g. the training
         features a Fisherfaces.compute just produced on the device)."""
         mid = self._metric()
-        if mid == _lib.METRIC_CHISQUARE or int(F.shape[0]) != len(self.X) or self._shard_info() is not None:
+        if mid in _lib.HIST_METRICS or int(F.shape[0]) != len(self.X) or self._shard_info() is not None:
             return
         with _DEVICE_LOCK:
             g = FloatGallery(F, mid)
@@ -249,10 +251,10 @@ class NearestNeighbor(AbstractClassifier):
         """Seed the ChiSquare gallery from device counts C [N][nbins] whose histograms (C / cell) are
         self.X (SpatialHistogram.compute just produced them on the device): no float64 upload."""
         mid = self._metric()
-        if mid != _lib.METRIC_CHISQUARE or int(C.shape[0]) != len(self.X) or self._shard_info() is not None:
+        if mid not in _lib.HIST_METRICS or int(C.shape[0]) != len(self.X) or self._shard_info() is not None:
             return
         with _DEVICE_LOCK:
-            g = Chi2Gallery.from_counts(C, count_bytes, float(cell))
+            g = Chi2Gallery.from_counts(C, count_bytes, float(cell), metric=mid)
             self.__dict__["_chi2_denom"] = float(cell)
             self.__dict__["_dev"] = ((mid, id(self.X), _lib.device()), len(self.X), g)
 
@@ -304,7 +306,7 @@ class NearestNeighbor(AbstractClassifier):
                 _, rank, ws = self._shard_info()
                 n0, n1 = shard_range(len(self.X), rank, ws)
                 feats = self._stack(self.X[n0:n1])
-            t = Chi2Gallery(feats)
+            t = Chi2Gallery(feats, metric=g.metric)
             t.index_base = getattr(g, "index_base", 0)
             tw = (g, g.N, t)
             self.__dict__["_dev_f32"] = tw

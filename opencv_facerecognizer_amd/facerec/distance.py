@@ -8,8 +8,12 @@ calls ``__call__`` per gallery item (the reference loop, classifier.py:104-108)
 but dispatches the whole gallery to the GPU.  ``__call__`` itself runs the same
 kernel on a 1x1 problem, so every distance value comes from the device path.
 
-Out of scope (not named by the hot path): NormalizedCorrelation,
-HistogramIntersection and the BinRatio family (distance.py:80-98, 119-183).
+The histogram metrics (HistogramIntersection and the BinRatio family,
+distance.py:119-183) search through ``ofr_hist_knn`` on the same counts / fp32
+galleries as ChiSquare.
+
+Out of scope (not named by the hot path): NormalizedCorrelation
+(distance.py:80-98).
 """
 from __future__ import annotations
 
@@ -43,8 +47,8 @@ def _pair(metric, p, q):
     q = np.asarray(q, dtype=np.float64).reshape(1, -1)
     if p.shape != q.shape:
         raise ValueError(f"operands could not be broadcast together with shapes {p.shape} {q.shape}")
-    if metric == _lib.METRIC_CHISQUARE:
-        g = Chi2Gallery(p)
+    if metric in _lib.HIST_METRICS:
+        g = Chi2Gallery(p, metric=metric)
         d, _ = g.search(g.query_rows(q), 1)
     else:
         g = FloatGallery(p, metric)
@@ -88,5 +92,56 @@ class ChiSquareDistance(AbstractDistance):
         return _pair(self.metric_id, p, q)
 
 
-for _c in (AbstractDistance, EuclideanDistance, CosineDistance, ChiSquareDistance):
+class HistogramIntersection(AbstractDistance):
+    """distance.py:119-126 -- sum(min(p, q)).  The reference classifier sorts every metric ascending
+    (classifier.py:113), so under this one the "nearest" row is the one with the SMALLEST overlap;
+    that order is kept."""
+
+    metric_id = _lib.METRIC_HISTINTERSECT
+
+    def __init__(self):
+        AbstractDistance.__init__(self, "HistogramIntersection")
+
+    def __call__(self, p, q):
+        return _pair(self.metric_id, p, q)
+
+
+class BinRatioDistance(AbstractDistance):
+    """distance.py:129-145 -- |sum(((p-q)^2 + 2a pq) / ((p+q)^2 + eps))|, a = |1 - p.q|."""
+
+    metric_id = _lib.METRIC_BINRATIO
+
+    def __init__(self):
+        AbstractDistance.__init__(self, "BinRatioDistance")
+
+    def __call__(self, p, q):
+        return _pair(self.metric_id, p, q)
+
+
+class L1BinRatioDistance(AbstractDistance):
+    """distance.py:148-164 -- the BinRatio terms times |p-q|."""
+
+    metric_id = _lib.METRIC_L1BINRATIO
+
+    def __init__(self):
+        AbstractDistance.__init__(self, "L1-BinRatioDistance")
+
+    def __call__(self, p, q):
+        return _pair(self.metric_id, p, q)
+
+
+class ChiSquareBRD(AbstractDistance):
+    """distance.py:167-183 -- the BinRatio numerators times (p-q)^2 over (p+q)^3 + eps."""
+
+    metric_id = _lib.METRIC_CHISQBRD
+
+    def __init__(self):
+        AbstractDistance.__init__(self, "ChiSquare-BinRatioDistance")
+
+    def __call__(self, p, q):
+        return _pair(self.metric_id, p, q)
+
+
+for _c in (AbstractDistance, EuclideanDistance, CosineDistance, ChiSquareDistance, HistogramIntersection,
+           BinRatioDistance, L1BinRatioDistance, ChiSquareBRD):
     _c.__module__ = "ocvfacerec.facerec.distance"

@@ -6,10 +6,11 @@ features never leave the GPU:
 * Fisherfaces + NearestNeighbor (Euclidean/Cosine): a batch of faces is
   projected (exact int8-slice MFMA kernel, the gallery centring folded into the
   projection's shift) and searched by the certified tiers;
-* LBPH, SpatialHistogram(ExtendedLBP) + NearestNeighbor(ChiSquare)
-  (feature.py:266-305, distance.py:101-116): ONE ``ofr_elbp_hist`` launch per
-  batch gives the integer cell histograms, searched as counts against the
-  counts gallery ``compute`` left on the device (``ofr_chi2_knn``).
+* LBPH, SpatialHistogram(ExtendedLBP) + NearestNeighbor(ChiSquare, or
+  HistogramIntersection / the BinRatio family) (feature.py:266-305,
+  distance.py:101-183): ONE ``ofr_elbp_hist`` launch per batch gives the
+  integer cell histograms, searched as counts against the counts gallery
+  ``compute`` left on the device (``ofr_chi2_knn`` / ``ofr_hist_knn``).
 """
 from __future__ import annotations
 
@@ -67,7 +68,7 @@ class PredictableModel(object):
     def _lbph(self):
         return (type(self.feature) is SpatialHistogram and isinstance(self.feature.lbp_operator, ExtendedLBP)
                 and type(self.classifier) is NearestNeighbor
-                and getattr(self.classifier.dist_metric, "metric_id", None) == 2)
+                and getattr(self.classifier.dist_metric, "metric_id", None) in _lib.HIST_METRICS)
 
     def _search_device(self, X, k=None):
         clf = self.classifier
