@@ -419,6 +419,34 @@ int ofr_elbp_hist_geom(void* stream, const uint8_t* imgs, int64_t n, int H, int 
                        const int32_t* offs_host, const double* w_host, int oy, int ox, int by, int bx,
                        int gr, int gc, void* counts, int count_bytes);
 
+/* OriginalLBP and LPQ + SpatialHistogram ---------------------------------------
+ * Replace OriginalLBP.__call__ lbp.py:55-72 and LPQ.__call__ lbp.py:211-318
+ * under SpatialHistogram.spatially_enhanced_histogram feature.py:286-302.
+ * imgs: uint8 [n][H][W] contiguous.  Both give 8-bit codes.
+ * OriginalLBP: codes uint8 [n][H-2][W-2], bit 7..0 = (neighbour >= centre) for
+ * NW, N, NE, E, SE, S, SW, W; bit-exact.
+ * LPQ: radius 1..8 (larger: OFR_E_UNSUPPORTED), window n = 2*radius+1, taps
+ * w0 = 1, w1(u) = exp(-2 pi i u / n), w2 = conj(w1); the four responses are the
+ * 'same' 2-D convolutions (zero outside the image) with (rows, columns) =
+ * (w0,w1), (w1,w0), (w1,w1), (w1,w2); F = their real and imaginary parts in that
+ * order, G = V^T F with V_host the 8x8 row-major matrix np.linalg.svd returns
+ * third (host memory, copied by the call), code = sum_k (G_k >= 0) 2^k, all in
+ * fp64.  codes: uint8 [n][H][W] in the reference's order: the code of pixel
+ * (r, c) is at linear index c*H + r of its image.  Exact wherever every |G_k|
+ * is above rounding noise (constant windows give G = 0 up to noise).
+ * counts: [n][gr*gc][256] of `count_bytes` (1, 2 or 4) unsigned integers,
+ * 4-byte aligned, cells cut from the code image as for ofr_elbp_hist_geom
+ * (py = floor(rows/gr), px = floor(cols/gc)); the float histogram of the
+ * reference is count / (py*px) exactly.  A grid larger than the code image or a
+ * count_bytes too narrow for py*px is OFR_E_INVALID.                          */
+int ofr_olbp_codes(void* stream, const uint8_t* imgs, int64_t n, int H, int W, uint8_t* codes);
+int ofr_olbp_hist(void* stream, const uint8_t* imgs, int64_t n, int H, int W, int gr, int gc,
+                  void* counts, int count_bytes);
+int ofr_lpq_codes(void* stream, const uint8_t* imgs, int64_t n, int H, int W, int radius,
+                  const double* V_host, uint8_t* codes);
+int ofr_lpq_hist(void* stream, const uint8_t* imgs, int64_t n, int H, int W, int radius,
+                 const double* V_host, int gr, int gc, void* counts, int count_bytes);
+
 /* Chi-square search ----------------------------------------------------------
  * Replaces ChiSquareDistance distance.py:112-116 inside NearestNeighbor.predict.
  * Q [B][ldq], G [N][ldg] rows of `nbins` values of type dtype (OFR_DT_*); the

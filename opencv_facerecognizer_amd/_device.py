@@ -1295,6 +1295,54 @@ def elbp_hist(imgs_u8, geom, grid, count_bytes=None):
     return out, cell, count_bytes
 
 
+def _count_bytes(cell, count_bytes):
+    if count_bytes is None:
+        count_bytes = 1 if cell <= 255 else (2 if cell <= 65535 else 4)
+    return count_bytes, {1: torch.uint8, 2: torch.int16, 4: torch.int32}[count_bytes]
+
+
+def olbp_codes(imgs_u8):
+    """OriginalLBP (lbp.py:55-72): uint8 [n][H][W] device tensor -> uint8 codes [n][H-2][W-2]."""
+    n, H, W = imgs_u8.shape
+    out = torch.empty((n, max(H - 2, 0), max(W - 2, 0)), dtype=torch.uint8, device=imgs_u8.device)
+    call("ofr_olbp_codes", stream(), ptr(imgs_u8), n, H, W, ptr(out))
+    return out
+
+
+def olbp_hist(imgs_u8, grid, count_bytes=None):
+    """-> (counts [n][gr*gc][256], cell pixel count, bytes per count), as elbp_hist."""
+    n, H, W = imgs_u8.shape
+    gr, gc = grid
+    cell = (max(H - 2, 0) // gr) * (max(W - 2, 0) // gc)
+    count_bytes, tdt = _count_bytes(cell, count_bytes)
+    out = torch.empty((n, gr * gc, 256), dtype=tdt, device=imgs_u8.device)
+    call("ofr_olbp_hist", stream(), ptr(imgs_u8), n, H, W, gr, gc, ptr(out), count_bytes)
+    return out, cell, count_bytes
+
+
+def lpq_codes(imgs_u8, radius, V):
+    """LPQ (lbp.py:211-318): uint8 [n][H][W] device tensor, V = LPQ.basis() -> uint8 codes [n][H][W] in the
+    reference's order."""
+    n, H, W = imgs_u8.shape
+    out = torch.empty((n, H, W), dtype=torch.uint8, device=imgs_u8.device)
+    V64 = np.ascontiguousarray(V, dtype=np.float64).reshape(8, 8)
+    call("ofr_lpq_codes", stream(), ptr(imgs_u8), n, H, W, radius, V64.ctypes.data_as(_lib.c_vp), ptr(out))
+    return out
+
+
+def lpq_hist(imgs_u8, radius, V, grid, count_bytes=None):
+    """-> (counts [n][gr*gc][256], cell pixel count, bytes per count), as elbp_hist."""
+    n, H, W = imgs_u8.shape
+    gr, gc = grid
+    cell = (H // gr) * (W // gc)
+    count_bytes, tdt = _count_bytes(cell, count_bytes)
+    out = torch.empty((n, gr * gc, 256), dtype=tdt, device=imgs_u8.device)
+    V64 = np.ascontiguousarray(V, dtype=np.float64).reshape(8, 8)
+    call("ofr_lpq_hist", stream(), ptr(imgs_u8), n, H, W, radius, V64.ctypes.data_as(_lib.c_vp), gr, gc, ptr(out),
+         count_bytes)
+    return out, cell, count_bytes
+
+
 # ---------------------------------------------------------------------------
 # training products  (feature.py:91-94, 162-168, 229)
 # ---------------------------------------------------------------------------

@@ -120,6 +120,10 @@ SIGNATURES = {
     "ofr_elbp_hist_geom": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int,
                                    c_int, c_int, c_vp, c_int]),
     "ofr_elbp_hist": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    "ofr_olbp_codes": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
+    "ofr_olbp_hist": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp, c_int]),
+    "ofr_lpq_codes": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp]),
+    "ofr_lpq_hist": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_int]),
     "ofr_chi2_workspace_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "ofr_chi2_mfma_bound": (c_dbl, [c_i64]),
     "ofr_chi2_table": (None, [c_vp]),

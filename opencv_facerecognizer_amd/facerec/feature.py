@@ -555,14 +555,14 @@ class Fisherfaces(_DeviceProjMixin, AbstractFeature):
         return "Fisherfaces (num_components=%s)" % (self.num_components)
 
 
-from .lbp import ExtendedLBP, LocalDescriptor  # noqa: E402  (feature.py:263)
+from .lbp import LPQ, ExtendedLBP, LocalDescriptor, OriginalLBP  # noqa: E402  (feature.py:263)
 
 
 class SpatialHistogram(AbstractFeature):
     """feature.py:266-305: per-cell LBP histograms, concatenated row-major over the grid.
 
-    The histograms are integer counts on the device (one ``ofr_elbp_hist`` launch per batch of
-    same-sized faces); the float64 histograms the reference API returns are count / (py * px),
+    The histograms are integer counts on the device (one ``ofr_elbp_hist`` / ``ofr_olbp_hist`` /
+    ``ofr_lpq_hist`` launch per batch of same-sized faces, by the operator's type); the float64 histograms the reference API returns are count / (py * px),
     which is exactly what numpy's ``np.histogram(..., density=True)`` gives for one cell
     (feature.py:298-299).  ``compute`` leaves the device counts for the classifier
     (``PredictableModel.compute``): the LBPH gallery stays resident as counts, never rebuilt from
@@ -589,14 +589,19 @@ class SpatialHistogram(AbstractFeature):
 
     def counts_device(self, imgs):
         """uint8 image stack (n,H,W) (host or device) -> (counts device tensor [n][cells][2^P], cell pixels, bytes)."""
-        if not isinstance(self.lbp_operator, ExtendedLBP):
-            raise NotImplementedError("SpatialHistogram (MI355X build) runs ExtendedLBP operators only")
+        op = self.lbp_operator
+        if not isinstance(op, (ExtendedLBP, OriginalLBP, LPQ)):
+            raise NotImplementedError("SpatialHistogram (MI355X build) runs ExtendedLBP, OriginalLBP and LPQ operators only")
         from .lbp import as_u8_images
         if not hasattr(imgs, "device"):
             imgs = as_u8_images(np.ascontiguousarray(imgs) if isinstance(imgs, np.ndarray) and imgs.ndim == 3
                                 else np.stack([np.asarray(x) for x in imgs]))
-        counts, cell, cb = _device.elbp_hist(_device.u8_images(imgs), self.lbp_operator.geometry(), tuple(self.sz))
-        return counts, cell, cb
+        imgs = _device.u8_images(imgs)
+        if isinstance(op, LPQ):
+            return _device.lpq_hist(imgs, int(op.radius), op.basis(), tuple(self.sz))
+        if isinstance(op, OriginalLBP):
+            return _device.olbp_hist(imgs, tuple(self.sz))
+        return _device.elbp_hist(imgs, op.geometry(), tuple(self.sz))
 
     def counts_batch(self, X):
         """Faces of one size (list, array [n][H][W] or a uint8 device tensor such as ``ingest.faces``

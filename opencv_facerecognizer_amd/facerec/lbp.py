@@ -7,8 +7,17 @@ exactly as the reference derives it (np.sin/np.cos, lbp.py:84-121); the codes
 are computed by the ``ofr_elbp_codes`` kernel, which reproduces the
 reference's float64 interpolation order bit for bit (see ofr_lbp.hip).
 
-Out of scope: OriginalLBP, VarLBP, LPQ (lbp.py:55-72, 140-318) — not on the
-hot path.
+``OriginalLBP`` (lbp.py:55-72) and ``LPQ`` (lbp.py:211-318) keep their
+constructor arguments, ``repr`` and pickled state; their 8-bit codes come from
+``ofr_olbp_codes`` / ``ofr_lpq_codes`` (ofr_lpq.hip).  OriginalLBP is
+bit-exact.  LPQ runs in fp64 with the decorrelation matrix ``V`` derived on
+the host (``LPQ.basis``) and agrees with the reference wherever the
+decorrelated responses are above rounding noise (on a window of
+constant grey every response is zero up to noise and the reference's own code
+is the sign of that noise).  All three take 8-bit grey images.
+
+Out of scope: VarLBP (lbp.py:140-208) — its values are real variances that
+mostly fall outside the histogram range.
 """
 from __future__ import annotations
 
@@ -67,7 +76,7 @@ def as_u8_images(X):
         Xi = X.astype(np.uint8)
         if np.array_equal(Xi.astype(X.dtype), X):
             return Xi
-    raise NotImplementedError("ExtendedLBP (MI355X build) accepts 8-bit grey images (integer values 0..255)")
+    raise NotImplementedError("the LBP operators (MI355X build) accept 8-bit grey images (integer values 0..255)")
 
 
 class ExtendedLBP(LocalDescriptor):
@@ -101,5 +110,96 @@ class ExtendedLBP(LocalDescriptor):
         return "ExtendedLBP (neighbors=%s, radius=%s)" % (self._neighbors, self._radius)
 
 
-for _c in (LocalDescriptor, ExtendedLBP):
+class OriginalLBP(LocalDescriptor):
+    """lbp.py:55-72 on the GPU: the 3x3 operator, codes [H-2][W-2]."""
+
+    def __init__(self):
+        LocalDescriptor.__init__(self, neighbors=8)
+
+    def __call__(self, X):
+        from .. import _device
+        X = as_u8_images(X)
+        if X.ndim != 2:
+            raise ValueError("OriginalLBP expects a 2-D image")
+        return _device.olbp_codes(_device.u8_images(X[None])).cpu().numpy()[0].astype(np.int64)
+
+    def __repr__(self):
+        return "OriginalLBP (neighbors=%s)" % (self._neighbors)
+
+
+_LPQ_BASIS = {}
+
+
+def lpq_basis(radius):
+    """lbp.py:244-276: the 8x8 matrix ``np.linalg.svd(D)`` returns third (the kernel applies its transpose).
+    Derived, not tabulated: the two largest singular values of D are equal, so the basis inside their
+    plane belongs to the host's LAPACK.  Cached per radius."""
+    if radius not in _LPQ_BASIS:
+        f = 1.0
+        x = np.arange(-radius, radius + 1)
+        n = len(x)
+        rho = 0.95
+        [xp, yp] = np.meshgrid(np.arange(1, (n + 1)), np.arange(1, (n + 1)))
+        pp = np.concatenate((xp, yp)).reshape(2, -1)
+        dd = _euc_dist(pp.T)
+        C = np.power(rho, dd)
+        w0 = (x * 0.0 + 1.0)
+        w1 = np.exp(-2 * np.pi * 1j * x * f / n)
+        w2 = np.conj(w1)
+        q1 = w0.reshape(-1, 1) * w1
+        q2 = w1.reshape(-1, 1) * w0
+        q3 = w1.reshape(-1, 1) * w1
+        q4 = w1.reshape(-1, 1) * w2
+        M = np.array([u.flatten('F') for q in (q1, q2, q3, q4) for u in (np.real(q), np.imag(q))])
+        D = np.dot(np.dot(M, C), M.T)
+        U, S, V = np.linalg.svd(D)
+        _LPQ_BASIS[radius] = np.ascontiguousarray(V, dtype=np.float64)
+    return _LPQ_BASIS[radius]
+
+
+def _euc_dist(X):
+    """lbp.py:231-241."""
+    Y = X = X.astype(float)
+    XX = np.sum(X * X, axis=1)[:, np.newaxis]
+    YY = XX.T
+    distances = np.dot(X, Y.T)
+    distances *= -2
+    distances += XX
+    distances += YY
+    np.maximum(distances, 0, distances)
+    distances.flat[::distances.shape[0] + 1] = 0.0
+    return np.sqrt(distances)
+
+
+class LPQ(LocalDescriptor):
+    """lbp.py:211-318 on the GPU: local phase quantization, codes [H][W] in the reference's order (the
+    code of pixel (r, c) sits at linear index c*H + r)."""
+
+    def __init__(self, radius=3):
+        LocalDescriptor.__init__(self, neighbors=8)
+        self._radius = radius
+
+    def euc_dist(self, X):
+        return _euc_dist(X)
+
+    def basis(self):
+        return lpq_basis(int(self._radius))
+
+    def __call__(self, X):
+        from .. import _device
+        X = as_u8_images(X)
+        if X.ndim != 2:
+            raise ValueError("LPQ expects a 2-D image")
+        codes = _device.lpq_codes(_device.u8_images(X[None]), int(self._radius), self.basis())
+        return codes.cpu().numpy()[0].astype(np.int64)
+
+    @property
+    def radius(self):
+        return self._radius
+
+    def __repr__(self):
+        return "LPQ (neighbors=%s, radius=%s)" % (self._neighbors, self._radius)
+
+
+for _c in (LocalDescriptor, ExtendedLBP, OriginalLBP, LPQ):
     _c.__module__ = "ocvfacerec.facerec.lbp"

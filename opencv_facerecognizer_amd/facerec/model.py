@@ -6,9 +6,10 @@ features never leave the GPU:
 * Fisherfaces + NearestNeighbor (Euclidean/Cosine): a batch of faces is
   projected (exact int8-slice MFMA kernel, the gallery centring folded into the
   projection's shift) and searched by the certified tiers;
-* LBPH, SpatialHistogram(ExtendedLBP) + NearestNeighbor(ChiSquare, or
-  HistogramIntersection / the BinRatio family) (feature.py:266-305,
-  distance.py:101-183): ONE ``ofr_elbp_hist`` launch per batch gives the
+* LBPH, SpatialHistogram(ExtendedLBP, OriginalLBP or LPQ) + NearestNeighbor(
+  ChiSquare, or HistogramIntersection / the BinRatio family) (feature.py:266-305,
+  distance.py:101-183): ONE histogram launch per batch (``ofr_elbp_hist``,
+  ``ofr_olbp_hist`` or ``ofr_lpq_hist``) gives the
   integer cell histograms, searched as counts against the counts gallery
   ``compute`` left on the device (``ofr_chi2_knn`` / ``ofr_hist_knn``).
 """
@@ -19,7 +20,7 @@ import numpy as np
 from .. import _lib
 from .classifier import AbstractClassifier, NearestNeighbor, results
 from .feature import AbstractFeature, Fisherfaces, SpatialHistogram
-from .lbp import ExtendedLBP
+from .lbp import LPQ, ExtendedLBP, OriginalLBP
 
 
 class PredictableModel(object):
@@ -66,7 +67,7 @@ class PredictableModel(object):
                 and getattr(self.classifier.dist_metric, "metric_id", None) in (0, 1))
 
     def _lbph(self):
-        return (type(self.feature) is SpatialHistogram and isinstance(self.feature.lbp_operator, ExtendedLBP)
+        return (type(self.feature) is SpatialHistogram and isinstance(self.feature.lbp_operator, (ExtendedLBP, OriginalLBP, LPQ))
                 and type(self.classifier) is NearestNeighbor
                 and getattr(self.classifier.dist_metric, "metric_id", None) in _lib.HIST_METRICS)
 
