@@ -447,6 +447,32 @@ int ofr_lpq_codes(void* stream, const uint8_t* imgs, int64_t n, int H, int W, in
 int ofr_lpq_hist(void* stream, const uint8_t* imgs, int64_t n, int H, int W, int radius,
                  const double* V_host, int gr, int gc, void* counts, int count_bytes);
 
+/* Illumination normalisation (reference preprocessing.py) --------------------
+ * imgs: uint8 [n][H][W] contiguous.
+ * ofr_tantriggs_f32 (preprocessing.py:98-105): X = v^gamma (256-entry table,
+ * fp64 pow rounded once to fp32); D = G(sigma1)*X - G(sigma0)*X, G =
+ * scipy.ndimage.gaussian_filter's defaults (radius int(4 sigma + 0.5),
+ * normalised exp(-x^2 / (2 sigma^2)), axis 0 then axis 1, border 'reflect');
+ * D /= mean(|D|^alpha)^(1/alpha); D /= mean(min(|D|, tau)^alpha)^(1/alpha);
+ * out = tau tanh(D / tau), fp32 [n][H][W].  sigma0, sigma1, alpha, tau > 0 and
+ * both radii <= 16 (sigma <= 4.125), else OFR_E_INVALID.  A face whose planes fit
+ * one workgroup's LDS is done in one launch; a larger one in row strips, with
+ * per-strip partial sums in `workspace` (ofr_tantriggs_workspace_bytes, 0 when
+ * not needed; 8-byte aligned) added in strip order: a face's result depends on
+ * nothing but the face and is the same from run to run.  A row so wide that not
+ * one strip row fits is OFR_E_UNSUPPORTED.  A constant face is 0/0 as in the
+ * reference: values unspecified (NaN), no trap.
+ * ofr_histeq_f64 (preprocessing.py:73-77 with density=True): np.histogram's
+ * uniform bins over [min, max] ([min-0.5, max+0.5] when equal), cdf = 255
+ * cumsum(h) / cumsum(h)[-1], out = np.interp(x, edges[:-1], cdf), fp64
+ * [n][H][W].  num_bins 1..4096, else OFR_E_INVALID.                            */
+size_t ofr_tantriggs_workspace_bytes(int64_t n, int H, int W, double sigma0, double sigma1);
+int ofr_tantriggs_f32(void* stream, const uint8_t* imgs, int64_t n, int H, int W, double alpha,
+                      double tau, double gamma, double sigma0, double sigma1, float* out,
+                      void* workspace, size_t workspace_bytes);
+int ofr_histeq_f64(void* stream, const uint8_t* imgs, int64_t n, int H, int W, int num_bins,
+                   double* out);
+
 /* Chi-square search ----------------------------------------------------------
  * Replaces ChiSquareDistance distance.py:112-116 inside NearestNeighbor.predict.
  * Q [B][ldq], G [N][ldg] rows of `nbins` values of type dtype (OFR_DT_*); the

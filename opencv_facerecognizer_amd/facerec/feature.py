@@ -137,10 +137,14 @@ class _DeviceProjMixin:
         return P.own_shift if extra is None else P.own_shift + extra
 
     def project_device(self, X, shift64=None, f64=False, ld=None):
-        """Batch of items -> (W^T x - own shift - shift64): fp32 search rows [B][ldy] or fp64 [B][d]."""
+        """Batch of items -> (W^T x - own shift - shift64): fp32 search rows [B][ldy] or fp64 [B][d].
+        Device tensors: uint8 faces (exact int8-slice kernel) or float32 / float64 rows [B][H][W] / [B][D]
+        (fp64 GEMM); any other dtype is a TypeError."""
         P = self._proj()
         sh = self._shift(P, shift64)
         if hasattr(X, "data_ptr"):      # device uint8 faces [B][H][W] / [B][D] (e.g. ingest.faces): no host trip
+            if X.dtype in (torch.float32, torch.float64):   # preprocessed faces (preprocessing.extract_batch)
+                return self._project_f64(_device.f64_dev(X.reshape(X.shape[0], -1)), P, sh, f64)
             if X.dtype != torch.uint8:
                 raise TypeError("device face batches must be uint8")
             return P.project(_device.u8_rows(X), shift64=sh, f64=f64)
@@ -151,7 +155,11 @@ class _DeviceProjMixin:
         A = X if isinstance(X, np.ndarray) and X.ndim == 2 and not isinstance(X, np.matrix) else _stack_rows(X)
         if A.dtype == np.uint8:
             return P.project(_device.u8_rows(A), shift64=sh, f64=f64)
-        Y = _device.gemm_f64(_device.f64_dev(A.astype(np.float64)), self._w64(P))
+        return self._project_f64(_device.f64_dev(A.astype(np.float64)), P, sh, f64)
+
+    def _project_f64(self, A, P, sh, f64):
+        """fp64 device rows [B][D] -> W^T x - shift on the fp64 MFMA GEMM."""
+        Y = _device.gemm_f64(A, self._w64(P))
         if sh is not None:
             Y = _device.center_f64(Y, sh)
         return Y if f64 else _device.center_round(Y, None, P.ldy)

@@ -11,7 +11,11 @@ features never leave the GPU:
   distance.py:101-183): ONE histogram launch per batch (``ofr_elbp_hist``,
   ``ofr_olbp_hist`` or ``ofr_lpq_hist``) gives the
   integer cell histograms, searched as counts against the counts gallery
-  ``compute`` left on the device (``ofr_chi2_knn`` / ``ofr_hist_knn``).
+  ``compute`` left on the device (``ofr_chi2_knn`` / ``ofr_hist_knn``);
+* ChainOperator(TanTriggsPreprocessing | HistogramEqualization, Fisherfaces) +
+  NearestNeighbor (Euclidean/Cosine): one preprocessing launch
+  (``ofr_tantriggs_f32`` / ``ofr_histeq_f64``), one fp64 projection with the
+  gallery centring folded in, one search.
 """
 from __future__ import annotations
 
@@ -21,6 +25,8 @@ from .. import _lib
 from .classifier import AbstractClassifier, NearestNeighbor, results
 from .feature import AbstractFeature, Fisherfaces, SpatialHistogram
 from .lbp import LPQ, ExtendedLBP, OriginalLBP
+from .operators import ChainOperator
+from .preprocessing import HistogramEqualization, TanTriggsPreprocessing
 
 
 class PredictableModel(object):
@@ -55,6 +61,8 @@ class PredictableModel(object):
 
     def predict(self, X):
         """model.py:53-55 (one face)."""
+        if self._chain():     # one face: the reference's own order, extract then classify
+            return self.classifier.predict(self.feature.extract(X))
         return self.predict_batch([X])[0]
 
     def search_batch(self, X, k=None):
@@ -64,6 +72,12 @@ class PredictableModel(object):
 
     def _fused(self):
         return (isinstance(self.feature, Fisherfaces) and type(self.classifier) is NearestNeighbor
+                and getattr(self.classifier.dist_metric, "metric_id", None) in (0, 1))
+
+    def _chain(self):
+        f = self.feature
+        return (type(f) is ChainOperator and type(f.model1) in (TanTriggsPreprocessing, HistogramEqualization)
+                and isinstance(f.model2, Fisherfaces) and type(self.classifier) is NearestNeighbor
                 and getattr(self.classifier.dist_metric, "metric_id", None) in (0, 1))
 
     def _lbph(self):
@@ -77,10 +91,14 @@ class PredictableModel(object):
         if self._lbph():
             return self._search_lbph(X, k)
         g = clf._gallery()
-        if g.N and g.d != self.feature._proj().d:
+        proj = self.feature
+        if self._chain():     # illumination normalisation on the device, its float faces go to the fp64 GEMM
+            proj = self.feature.model2
+            X = self.feature.model1.extract_batch(X)
+        if g.N and g.d != proj._proj().d:
             raise ValueError("feature dimension does not match the classifier gallery")
         # Euclidean: the gallery centring is folded into the projection (W^T x - c, fp64, rounded once)
-        Qd = self.feature.project_device(X, shift64=g.shift64)
+        Qd = proj.project_device(X, shift64=g.shift64)
         return clf._search_prepared(Qd, k)
 
     def _search_lbph(self, X, k):
@@ -116,7 +134,7 @@ class PredictableModel(object):
     def predict_batch(self, X):
         """Predict a batch of faces (list of 2-D arrays, an array [B, H, W], or a uint8 device
         tensor [B, H, W] such as ``ingest.faces`` returns)."""
-        if not (self._fused() or self._lbph()):
+        if not (self._fused() or self._lbph() or self._chain()):
             if hasattr(X, "data_ptr"):   # a device face batch: the generic path works on host items
                 X = list(X.cpu().numpy())
             qs = [self.feature.extract(x) for x in X]

@@ -36,6 +36,17 @@ class ChainOperator(FeatureOperator):
         X = self.model1.extract(X)
         return self.model2.extract(X)
 
+    def extract_batch(self, X):
+        """Batch of extract: model1's ``extract_batch`` where it has one, and its device result goes
+        straight to model2's ``project_device`` (fp64 device rows [B][d]) or ``extract_batch``."""
+        batch1 = getattr(self.model1, "extract_batch", None)
+        X = batch1(X) if batch1 is not None else [self.model1.extract(x) for x in X]
+        if hasattr(self.model2, "project_device"):
+            return self.model2.project_device(X, f64=True)
+        if hasattr(self.model2, "extract_batch"):
+            return self.model2.extract_batch(X)
+        return [self.model2.extract(x) for x in (X.cpu().numpy() if hasattr(X, "data_ptr") else X)]
+
     def __repr__(self):
         return "ChainOperator(" + repr(self.model1) + "," + repr(self.model2) + ")"
 

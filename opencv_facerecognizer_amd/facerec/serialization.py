@@ -46,9 +46,9 @@ def _numpy1_globals(data):
 
 def _model_classes():
     from ..trainer.thetrainer import ExtendedPredictableModel
-    from . import classifier, distance, feature, lbp, model, operators
+    from . import classifier, distance, feature, lbp, model, operators, preprocessing
     classes = {}
-    for mod in (classifier, distance, feature, lbp, model, operators):
+    for mod in (classifier, distance, feature, lbp, model, operators, preprocessing):
         for name in dir(mod):
             obj = getattr(mod, name)
             if isinstance(obj, type) and getattr(obj, "__module__", "").startswith("ocvfacerec."):
