@@ -51,6 +51,8 @@ enum ofr_metric {
   OFR_METRIC_BINRATIO = 4,      /* :129-145 |sum(((p-q)^2 + 2a pq) / ((p+q)^2+eps))|          */
   OFR_METRIC_L1BINRATIO = 5,    /* :148-164 the same, numerator times |p-q|                   */
   OFR_METRIC_CHISQBRD = 6,      /* :167-183 numerator times (p-q)^2, denominator (p+q)^3+eps  */
+  /* ofr_ncorr_knn, ofr_knn_deep; pm = p - mean(p), qm = q - mean(q)            */
+  OFR_METRIC_NCORR = 7,         /* :80-98 1 - pm.qm / (|pm| |qm|)                               */
 };
 
 enum ofr_dtype { OFR_DT_U8 = 0, OFR_DT_U16 = 1, OFR_DT_U32 = 2, OFR_DT_F32 = 3, OFR_DT_F64 = 4 };
@@ -377,7 +379,7 @@ int ofr_knn_f6x2(void* stream, int phases, const float* Q, int64_t B, int64_t ld
  * above do not serve -- they keep 16 candidates per tile): the reference's distance of every
  * (query, row) pair in fp64 (Euclidean distance.py:57-60, Cosine :74-77 with NaN for a zero row,
  * ChiSquare :112-116, the four histogram metrics :119-183 as T1 + 2 |1 - p.q| T2 with the three
- * sums kept per pair), then per query the k smallest by (distance, row), NaN last.  Q [B][ldq] of
+ * sums kept per pair, NormalizedCorrelation :92-98 on rows centred by their means), then per query the k smallest by (distance, row), NaN last.  Q [B][ldq] of
  * qdtype, G [N][ldg] of gdtype (OFR_DT_*; integer rows are counts, value = count / denom as the
  * reference's float64 histograms; denom 1 for float rows).  out_d / out_i [B][k]; entries past
  * min(k, N) are (+inf, -1).  Any k: min(k, N) <= 4096 by a radix select in LDS, above it by a
@@ -521,6 +523,24 @@ size_t ofr_hist_workspace_bytes(int64_t B, int64_t N, int k);
 int ofr_hist_knn(void* stream, int metric, int dtype, const void* Q, int64_t B, int64_t ldq, const void* G,
                  int64_t N, int64_t ldg, int64_t nbins, double denom, int k, int64_t index_base, double* out_d,
                  int64_t* out_i, void* workspace, size_t workspace_bytes, int* cert);
+
+/* NormalizedCorrelation search -------------------------------------------------
+ * Replaces NormalizedCorrelation (distance.py:80-98) inside NearestNeighbor.predict:
+ * d = 1 - (p - pm).(q - qm) / (|p - pm| |q - qm|), in [0, 2], NaN for a constant row (ranked last).
+ * Arguments, alignment, outputs and the k <= OFR_MAX_K limit as ofr_chi2_knn; the value is invariant
+ * under scaling, so counts take no denominator.  Row statistics (mean, 1 / norm of the centred row) of
+ * both operands are formed per call in the workspace.  Coarse pass: uint8 counts of fewer than 2^17
+ * padded bins on v_mfma_i32_32x32x32_i8 with the exact integer dot product (bytes at or past nbins
+ * are masked, whatever the pad holds); every other type centred to fp32 with an fp32 FMA dot.  The
+ * best 16 rows per tile are re-evaluated with the reference formula in fp64; cert[q] = 1 iff the
+ * k-th exact distance lies below the 16th coarse key minus an absolute bound (2^-23 + ... for the
+ * MFMA pass, + 1.0625 (nbins + 2) 2^-24 for the fp32 one; a constant query, and a tile holding a
+ * uint32 count >= 2^24, certify nothing).  Queries with cert 0 (and k > OFR_MAX_K) are served by
+ * ofr_knn_deep with OFR_METRIC_NCORR.                                                        */
+size_t ofr_ncorr_workspace_bytes(int64_t B, int64_t N, int k);
+int ofr_ncorr_knn(void* stream, int dtype, const void* Q, int64_t B, int64_t ldq, const void* G, int64_t N,
+                  int64_t ldg, int64_t nbins, int k, int64_t index_base, double* out_d, int64_t* out_i,
+                  void* workspace, size_t workspace_bytes, int* cert);
 
 /* Training (PCA Gram / LDA scatter) ----------------------------------------
  * C[M][N] = alpha * op(A) op(B) + beta * C in fp64 on the fp64 MFMA

@@ -1176,10 +1176,17 @@ class Chi2Gallery:
         out_d = torch.empty((B, k), dtype=torch.float64, device=Qd.device)
         out_i = torch.empty((B, k), dtype=torch.int64, device=Qd.device)
         cert = torch.empty(B, dtype=torch.int32, device=Qd.device)
-        ws = self.ws.get(_lib.load().ofr_hist_workspace_bytes(B, self.N, k), Qd.device)
-        call("ofr_hist_knn", stream(), self.metric, self.dtype, ptr(Qd), B, Qd.shape[1], ptr(self.G), self.N,
-             self.G.shape[1], self.nbins, self.denom, k, index_base, ptr(out_d), ptr(out_i), ptr(ws), ws.numel(),
-             ptr(cert))
+        if self.metric == _lib.METRIC_NCORR:
+            # NormalizedCorrelation (ofr_ncorr_knn): uint8 counts on the int8 MFMA with the exact integer dot
+            # product, other rows centred to fp32; scale-invariant, so the counts' denominator plays no part
+            ws = self.ws.get(_lib.load().ofr_ncorr_workspace_bytes(B, self.N, k), Qd.device)
+            call("ofr_ncorr_knn", stream(), self.dtype, ptr(Qd), B, Qd.shape[1], ptr(self.G), self.N,
+                 self.G.shape[1], self.nbins, k, index_base, ptr(out_d), ptr(out_i), ptr(ws), ws.numel(), ptr(cert))
+        else:
+            ws = self.ws.get(_lib.load().ofr_hist_workspace_bytes(B, self.N, k), Qd.device)
+            call("ofr_hist_knn", stream(), self.metric, self.dtype, ptr(Qd), B, Qd.shape[1], ptr(self.G), self.N,
+                 self.G.shape[1], self.nbins, self.denom, k, index_base, ptr(out_d), ptr(out_i), ptr(ws), ws.numel(),
+                 ptr(cert))
         rows = open_rows(cert)
         if rows.numel():
             sub = Qd.index_select(0, rows).contiguous()

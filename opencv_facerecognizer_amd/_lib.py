@@ -25,9 +25,10 @@ METRIC_HISTINTERSECT = 3
 METRIC_BINRATIO = 4
 METRIC_L1BINRATIO = 5
 METRIC_CHISQBRD = 6
+METRIC_NCORR = 7
 # the metrics of histogram rows (counts / denom or fp32 values), served by _device.Chi2Gallery
 HIST_METRICS = frozenset((METRIC_CHISQUARE, METRIC_HISTINTERSECT, METRIC_BINRATIO, METRIC_L1BINRATIO,
-                          METRIC_CHISQBRD))
+                          METRIC_CHISQBRD, METRIC_NCORR))
 MAX_K = 16
 DT_U8, DT_U16, DT_U32, DT_F32, DT_F64 = 0, 1, 2, 3, 4
 
@@ -138,6 +139,9 @@ SIGNATURES = {
     "ofr_hist_workspace_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "ofr_hist_knn": (c_int, [c_vp, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_dbl, c_int, c_i64,
                              c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ofr_ncorr_workspace_bytes": (c_sz, [c_i64, c_i64, c_int]),
+    "ofr_ncorr_knn": (c_int, [c_vp, c_int, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_vp, c_vp,
+                              c_vp, c_sz, c_vp]),
     "ofr_gemm_f64": (c_int, [c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_dbl, c_vp, c_i64, c_vp, c_i64, c_dbl, c_vp,
                              c_i64]),
     "ofr_center_u8_f64": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64]),

@@ -9,7 +9,9 @@
 //                      (:74-77, NaN for a zero row as numpy's 0/0), ChiSquare
 //                      sum (p - q)^2 / (p + q + eps) (:112-116), HistogramIntersection sum min(p, q)
 //                      (:126), the bin-ratio forms (:129-183) as T1 + 2 |1 - p.q| T2 with T1, T2 and
-//                      p.q summed per pair and combined at the end -- on 64 x 64 tiles with the
+//                      p.q summed per pair and combined at the end, NormalizedCorrelation
+//                      1 - pm.qm / (|pm| |qm|) on rows centred by their means (:92-98; the means of
+//                      the tile's rows first, NaN for a constant row) -- on 64 x 64 tiles with the
 //                      features staged through LDS (fp32 rows, or count rows / denom: the
 //                      reference's float64 histogram values bit for bit);
 //   deep_select_kernel per query the k smallest (distance, row) pairs: an 8-pass radix select of
@@ -72,6 +74,27 @@ __global__ void __launch_bounds__(256) deep_dist_kernel(DistArgs a) {
   // bin-ratio forms (distance.py:129-183): acc = T1, acc2 = T2, dotp = p.q, combined at the end
   constexpr bool BINRATIO = METRIC == OFR_METRIC_BINRATIO || METRIC == OFR_METRIC_L1BINRATIO ||
                             METRIC == OFR_METRIC_CHISQBRD;
+  constexpr bool NCORR = METRIC == OFR_METRIC_NCORR;
+  __shared__ double qmean[NCORR ? TQ : 1], gmean[NCORR ? TG : 1];   // NCORR: the tile's row means
+  if constexpr (NCORR) {
+    // four threads per row sum it in feature order, strided; rows past B / N have mean 0
+    const int r = t >> 2, part = t & 3;
+    const int64_t q = q0 + r, g = g0 + r;
+    double sq = 0.0, sg = 0.0;
+    for (int64_t k = part; k < a.d; k += 4) {
+      if (q < a.B) sq += val(a.Q, a.qdt, q * a.ldq + k, a.denom);
+      if (g < a.N) sg += val(a.G, a.gdt, g * a.ldg + k, a.denom);
+    }
+    sq += __shfl_xor(sq, 1);
+    sq += __shfl_xor(sq, 2);
+    sg += __shfl_xor(sg, 1);
+    sg += __shfl_xor(sg, 2);
+    if (part == 0) {
+      qmean[r] = sq / (double)a.d;
+      gmean[r] = sg / (double)a.d;
+    }
+    __syncthreads();
+  }
   double acc[4][4], acc2[4][4], dotp[4][4], qq[4], gg[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -84,8 +107,8 @@ __global__ void __launch_bounds__(256) deep_dist_kernel(DistArgs a) {
     for (int e = t; e < KB * TQ; e += 256) {
       const int r = e / KB, c = e % KB;
       const int64_t k = k0 + c, q = q0 + r, g = g0 + r;
-      qs[c][r] = (k < a.d && q < a.B) ? val(a.Q, a.qdt, q * a.ldq + k, a.denom) : 0.0;
-      gs[c][r] = (k < a.d && g < a.N) ? val(a.G, a.gdt, g * a.ldg + k, a.denom) : 0.0;
+      qs[c][r] = (k < a.d && q < a.B) ? val(a.Q, a.qdt, q * a.ldq + k, a.denom) - (NCORR ? qmean[r] : 0.0) : 0.0;
+      gs[c][r] = (k < a.d && g < a.N) ? val(a.G, a.gdt, g * a.ldg + k, a.denom) - (NCORR ? gmean[r] : 0.0) : 0.0;
     }
     __syncthreads();
     const int kn = a.d - k0 < KB ? (int)(a.d - k0) : KB;
@@ -96,7 +119,7 @@ __global__ void __launch_bounds__(256) deep_dist_kernel(DistArgs a) {
         qv[i] = qs[c][ty + 16 * i];
         gv[i] = gs[c][tx + 16 * i];
       }
-      if constexpr (METRIC == OFR_METRIC_COSINE) {
+      if constexpr (METRIC == OFR_METRIC_COSINE || NCORR) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           qq[i] = fma(qv[i], qv[i], qq[i]);
@@ -110,7 +133,7 @@ __global__ void __launch_bounds__(256) deep_dist_kernel(DistArgs a) {
           if constexpr (METRIC == OFR_METRIC_EUCLIDEAN) {
             const double df = qv[i] - gv[j];
             acc[i][j] = fma(df, df, acc[i][j]);
-          } else if constexpr (METRIC == OFR_METRIC_COSINE) {
+          } else if constexpr (METRIC == OFR_METRIC_COSINE || NCORR) {
             acc[i][j] = fma(qv[i], gv[j], acc[i][j]);
           } else if constexpr (METRIC == OFR_METRIC_HISTINTERSECT) {
             acc[i][j] += fmin(qv[i], gv[j]);   // distance.py:126
@@ -140,6 +163,7 @@ __global__ void __launch_bounds__(256) deep_dist_kernel(DistArgs a) {
       double v = acc[i][j];
       if constexpr (METRIC == OFR_METRIC_EUCLIDEAN) v = sqrt(v);
       if constexpr (METRIC == OFR_METRIC_COSINE) v = -v / sqrt(qq[i] * gg[j]);   // 0 / 0 = NaN, as numpy
+      if constexpr (NCORR) v = 1.0 - v / (sqrt(gg[j]) * sqrt(qq[i]));              // distance.py:98
       if constexpr (BINRATIO) v = fabs(v + 2.0 * fabs(1.0 - dotp[i][j]) * acc2[i][j]);
       a.D[q * a.N + g] = v;
     }
@@ -311,7 +335,7 @@ extern "C" int ofr_knn_deep(void* stream, int metric, const void* Q, int64_t B, 
                             const void* G, int64_t N, int64_t ldg, int gdtype, int64_t d, double denom, int k,
                             int64_t index_base, double* out_d, int64_t* out_i, void* workspace,
                             size_t workspace_bytes) {
-  OFR_CHECK_ARG(metric >= OFR_METRIC_EUCLIDEAN && metric <= OFR_METRIC_CHISQBRD, "ofr_knn_deep: unknown metric");
+  OFR_CHECK_ARG(metric >= OFR_METRIC_EUCLIDEAN && metric <= OFR_METRIC_NCORR, "ofr_knn_deep: unknown metric");
   OFR_CHECK_ARG(B >= 0 && N >= 0 && d >= 1 && ldq >= d && ldg >= d && k >= 1, "ofr_knn_deep: bad sizes");
   OFR_CHECK_ARG(qdtype >= OFR_DT_U8 && qdtype <= OFR_DT_F64 && gdtype >= OFR_DT_U8 && gdtype <= OFR_DT_F64,
                 "ofr_knn_deep: bad dtype");
@@ -365,8 +389,10 @@ extern "C" int ofr_knn_deep(void* stream, int metric, const void* Q, int64_t B, 
         hipLaunchKernelGGL(deep::deep_dist_kernel<OFR_METRIC_BINRATIO>, grid, dim3(256), 0, st, a);
       else if (metric == OFR_METRIC_L1BINRATIO)
         hipLaunchKernelGGL(deep::deep_dist_kernel<OFR_METRIC_L1BINRATIO>, grid, dim3(256), 0, st, a);
-      else
+      else if (metric == OFR_METRIC_CHISQBRD)
         hipLaunchKernelGGL(deep::deep_dist_kernel<OFR_METRIC_CHISQBRD>, grid, dim3(256), 0, st, a);
+      else
+        hipLaunchKernelGGL(deep::deep_dist_kernel<OFR_METRIC_NCORR>, grid, dim3(256), 0, st, a);
       OFR_LAUNCH_CHECK("deep_dist_kernel");
     }
     if (sorted) {

@@ -140,7 +140,7 @@ class NearestNeighbor(AbstractClassifier):
         if mid is None:
             raise NotImplementedError(
                 f"{self.dist_metric!r} has no device kernel (supported: Euclidean, Cosine, ChiSquare, "
-                "HistogramIntersection, BinRatio, L1-BinRatio, ChiSquare-BinRatio)")
+                "HistogramIntersection, BinRatio, L1-BinRatio, ChiSquare-BinRatio, NormalizedCorrelation)")
         return mid
 
     def _invalidate(self):

@@ -10,10 +10,8 @@ kernel on a 1x1 problem, so every distance value comes from the device path.
 
 The histogram metrics (HistogramIntersection and the BinRatio family,
 distance.py:119-183) search through ``ofr_hist_knn`` on the same counts / fp32
-galleries as ChiSquare.
-
-Out of scope (not named by the hot path): NormalizedCorrelation
-(distance.py:80-98).
+galleries as ChiSquare; NormalizedCorrelation (distance.py:80-98) through
+``ofr_ncorr_knn`` on them as well.
 """
 from __future__ import annotations
 
@@ -75,6 +73,19 @@ class CosineDistance(AbstractDistance):
 
     def __init__(self):
         AbstractDistance.__init__(self, "CosineDistance")
+
+    def __call__(self, p, q):
+        return _pair(self.metric_id, p, q)
+
+
+class NormalizedCorrelation(AbstractDistance):
+    """distance.py:80-98 -- 1 - pm.qm / (|pm| |qm|) with pm = p - mean(p), qm = q - mean(q); NaN for a
+    constant vector (0 / 0, as numpy), which the classifier ranks last."""
+
+    metric_id = _lib.METRIC_NCORR
+
+    def __init__(self):
+        AbstractDistance.__init__(self, "NormalizedCorrelation")
 
     def __call__(self, p, q):
         return _pair(self.metric_id, p, q)
@@ -142,6 +153,6 @@ class ChiSquareBRD(AbstractDistance):
         return _pair(self.metric_id, p, q)
 
 
-for _c in (AbstractDistance, EuclideanDistance, CosineDistance, ChiSquareDistance, HistogramIntersection,
+for _c in (AbstractDistance, EuclideanDistance, CosineDistance, NormalizedCorrelation, ChiSquareDistance, HistogramIntersection,
            BinRatioDistance, L1BinRatioDistance, ChiSquareBRD):
     _c.__module__ = "ocvfacerec.facerec.distance"
