@@ -449,6 +449,38 @@ int ofr_lpq_codes(void* stream, const uint8_t* imgs, int64_t n, int H, int W, in
 int ofr_lpq_hist(void* stream, const uint8_t* imgs, int64_t n, int H, int W, int radius,
                  const double* V_host, int gr, int gc, void* counts, int count_bytes);
 
+/* The three descriptors on float images ------------------------------------------
+ * The float twins of the six entry points above: imgs [n][H][W] contiguous,
+ * float32 (pixel_bytes = 4) or float64 (pixel_bytes = 8) of arbitrary values, as
+ * ofr_tantriggs_f32 / ofr_histeq_f64 return; any other pixel_bytes is
+ * OFR_E_INVALID.  Every pixel is converted exactly to fp64 and all arithmetic is
+ * fp64 (ExtendedLBP and OriginalLBP without contraction), as numpy 2.x runs the
+ * reference on a float image (lbp.py:59-69, 80-130, 243-311).  Outputs, grids,
+ * count_bytes and errors are those of the byte twin.
+ * OriginalLBP: >= on the values as given; bit-exact.
+ * ExtendedLBP: N as for ofr_elbp_codes; the centre is the reference's
+ *   np.asarray(X, dtype=np.uint8) (lbp.py:104): C = (double)((int64)trunc(x) & 255),
+ *   floor for 0 <= x < 256 and wrap-around outside (-3.7 -> 253, 300.7 -> 44);
+ *   bit-exact.  Counts also where grid_cols * 2^P counters exceed a workgroup's LDS
+ *   (packed global atomics; one image's counts must then fill whole 32-bit words).
+ * LPQ: the formulation of ofr_lpq_codes with the float pixel in place of the byte.
+ * Non-finite pixels: the codes that touch them are unspecified; nothing traps
+ * and every code stays inside the histogram range.                               */
+int ofr_elbp_codes_f(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W, int P,
+                     const int32_t* offs_host, const double* w_host, int oy, int ox, int by, int bx,
+                     uint32_t* codes);
+int ofr_elbp_hist_f(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W, int P,
+                    const int32_t* offs_host, const double* w_host, int oy, int ox, int by, int bx,
+                    int gr, int gc, void* counts, int count_bytes);
+int ofr_olbp_codes_f(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W,
+                     uint8_t* codes);
+int ofr_olbp_hist_f(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W, int gr,
+                    int gc, void* counts, int count_bytes);
+int ofr_lpq_codes_f(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W, int radius,
+                    const double* V_host, uint8_t* codes);
+int ofr_lpq_hist_f(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W, int radius,
+                   const double* V_host, int gr, int gc, void* counts, int count_bytes);
+
 /* Illumination normalisation (reference preprocessing.py) --------------------
  * imgs: uint8 [n][H][W] contiguous.
  * ofr_tantriggs_f32 (preprocessing.py:98-105): X = v^gamma (256-entry table,

@@ -142,6 +142,27 @@ def u8_images(a, device=None):
     return torch.from_numpy(np.ascontiguousarray(arr)).to(device)
 
 
+_PIXEL_DTYPES = (torch.uint8, torch.float32, torch.float64)
+
+
+def pixel_images(a, device=None):
+    """Image stack (n, H, W) of uint8, float32 or float64 (host array or device tensor) -> contiguous device
+    tensor of the same dtype: what the LBP kernels take.  Any other dtype is a TypeError, never a cast."""
+    device = device or dev()
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+    if t.dtype not in _PIXEL_DTYPES or t.dim() != 3:
+        raise TypeError("expected a uint8, float32 or float64 image stack (n, H, W), got %s %s"
+                        % (t.dtype, tuple(t.shape)))
+    return t.to(device).contiguous()
+
+
+def _pixel_bytes(imgs):
+    """0 for uint8 images (the byte kernels), else the float pixel's width (the *_f kernels)."""
+    if imgs.dtype not in _PIXEL_DTYPES:
+        raise TypeError("LBP images must be uint8, float32 or float64, got %s" % imgs.dtype)
+    return 0 if imgs.dtype == torch.uint8 else imgs.element_size()
+
+
 def f64_dev(a, device=None):
     device = device or dev()
     if isinstance(a, torch.Tensor):
@@ -1269,21 +1290,28 @@ def topk_merge(in_d, in_i, P, kin, k):
 # LBP  (lbp.py:80-130, feature.py:286-302)
 # ---------------------------------------------------------------------------
 def elbp_codes(imgs_u8, geom):
-    """imgs: uint8 [n][H][W] device tensor; geom: lbp geometry tuple -> uint32 codes as int64 [n][dy][dx]."""
+    """imgs: uint8, float32 or float64 [n][H][W] device tensor (contiguous; float images take the
+    ofr_*_f kernels, here and in the five functions below); geom: lbp geometry tuple -> uint32 codes as
+    int32 storage [n][dy][dx]."""
     (oy, ox), (by, bx), offs, wts = geom
+    pb = _pixel_bytes(imgs_u8)
     n, H, W = imgs_u8.shape
     dy, dx = H - by + 1, W - bx + 1
     out = torch.empty((n, max(dy, 0), max(dx, 0)), dtype=torch.int32, device=imgs_u8.device)
     offs32 = np.ascontiguousarray(offs, dtype=np.int32)
     w64 = np.ascontiguousarray(wts, dtype=np.float64)
-    call("ofr_elbp_codes", stream(), ptr(imgs_u8), n, H, W, len(offs32), offs32.ctypes.data_as(_lib.c_vp),
-         w64.ctypes.data_as(_lib.c_vp), oy, ox, by, bx, ptr(out))
+    geom_args = (len(offs32), offs32.ctypes.data_as(_lib.c_vp), w64.ctypes.data_as(_lib.c_vp), oy, ox, by, bx)
+    if pb:
+        call("ofr_elbp_codes_f", stream(), ptr(imgs_u8), pb, n, H, W, *geom_args, ptr(out))
+    else:
+        call("ofr_elbp_codes", stream(), ptr(imgs_u8), n, H, W, *geom_args, ptr(out))
     return out  # int32 storage of uint32 codes (reinterpret on host)
 
 
 def elbp_hist(imgs_u8, geom, grid, count_bytes=None):
     """-> (counts device tensor [n][gr*gc][2^P] of uint8/int16/int32 storage, cell pixel count)."""
     (oy, ox), (by, bx), offs, wts = geom
+    pb = _pixel_bytes(imgs_u8)
     n, H, W = imgs_u8.shape
     P = len(offs)
     gr, gc = grid
@@ -1297,8 +1325,11 @@ def elbp_hist(imgs_u8, geom, grid, count_bytes=None):
     out = torch.empty((n, gr * gc, 1 << P), dtype=tdt, device=imgs_u8.device)
     offs32 = np.ascontiguousarray(offs, dtype=np.int32)
     w64 = np.ascontiguousarray(wts, dtype=np.float64)
-    call("ofr_elbp_hist_geom", stream(), ptr(imgs_u8), n, H, W, P, offs32.ctypes.data_as(_lib.c_vp),
-         w64.ctypes.data_as(_lib.c_vp), oy, ox, by, bx, gr, gc, ptr(out), count_bytes)
+    geom_args = (P, offs32.ctypes.data_as(_lib.c_vp), w64.ctypes.data_as(_lib.c_vp), oy, ox, by, bx)
+    if pb:
+        call("ofr_elbp_hist_f", stream(), ptr(imgs_u8), pb, n, H, W, *geom_args, gr, gc, ptr(out), count_bytes)
+    else:
+        call("ofr_elbp_hist_geom", stream(), ptr(imgs_u8), n, H, W, *geom_args, gr, gc, ptr(out), count_bytes)
     return out, cell, count_bytes
 
 
@@ -1312,7 +1343,11 @@ def olbp_codes(imgs_u8):
     """OriginalLBP (lbp.py:55-72): uint8 [n][H][W] device tensor -> uint8 codes [n][H-2][W-2]."""
     n, H, W = imgs_u8.shape
     out = torch.empty((n, max(H - 2, 0), max(W - 2, 0)), dtype=torch.uint8, device=imgs_u8.device)
-    call("ofr_olbp_codes", stream(), ptr(imgs_u8), n, H, W, ptr(out))
+    pb = _pixel_bytes(imgs_u8)
+    if pb:
+        call("ofr_olbp_codes_f", stream(), ptr(imgs_u8), pb, n, H, W, ptr(out))
+    else:
+        call("ofr_olbp_codes", stream(), ptr(imgs_u8), n, H, W, ptr(out))
     return out
 
 
@@ -1323,7 +1358,11 @@ def olbp_hist(imgs_u8, grid, count_bytes=None):
     cell = (max(H - 2, 0) // gr) * (max(W - 2, 0) // gc)
     count_bytes, tdt = _count_bytes(cell, count_bytes)
     out = torch.empty((n, gr * gc, 256), dtype=tdt, device=imgs_u8.device)
-    call("ofr_olbp_hist", stream(), ptr(imgs_u8), n, H, W, gr, gc, ptr(out), count_bytes)
+    pb = _pixel_bytes(imgs_u8)
+    if pb:
+        call("ofr_olbp_hist_f", stream(), ptr(imgs_u8), pb, n, H, W, gr, gc, ptr(out), count_bytes)
+    else:
+        call("ofr_olbp_hist", stream(), ptr(imgs_u8), n, H, W, gr, gc, ptr(out), count_bytes)
     return out, cell, count_bytes
 
 
@@ -1333,7 +1372,11 @@ def lpq_codes(imgs_u8, radius, V):
     n, H, W = imgs_u8.shape
     out = torch.empty((n, H, W), dtype=torch.uint8, device=imgs_u8.device)
     V64 = np.ascontiguousarray(V, dtype=np.float64).reshape(8, 8)
-    call("ofr_lpq_codes", stream(), ptr(imgs_u8), n, H, W, radius, V64.ctypes.data_as(_lib.c_vp), ptr(out))
+    pb = _pixel_bytes(imgs_u8)
+    if pb:
+        call("ofr_lpq_codes_f", stream(), ptr(imgs_u8), pb, n, H, W, radius, V64.ctypes.data_as(_lib.c_vp), ptr(out))
+    else:
+        call("ofr_lpq_codes", stream(), ptr(imgs_u8), n, H, W, radius, V64.ctypes.data_as(_lib.c_vp), ptr(out))
     return out
 
 
@@ -1345,8 +1388,13 @@ def lpq_hist(imgs_u8, radius, V, grid, count_bytes=None):
     count_bytes, tdt = _count_bytes(cell, count_bytes)
     out = torch.empty((n, gr * gc, 256), dtype=tdt, device=imgs_u8.device)
     V64 = np.ascontiguousarray(V, dtype=np.float64).reshape(8, 8)
-    call("ofr_lpq_hist", stream(), ptr(imgs_u8), n, H, W, radius, V64.ctypes.data_as(_lib.c_vp), gr, gc, ptr(out),
-         count_bytes)
+    pb = _pixel_bytes(imgs_u8)
+    if pb:
+        call("ofr_lpq_hist_f", stream(), ptr(imgs_u8), pb, n, H, W, radius, V64.ctypes.data_as(_lib.c_vp), gr, gc,
+             ptr(out), count_bytes)
+    else:
+        call("ofr_lpq_hist", stream(), ptr(imgs_u8), n, H, W, radius, V64.ctypes.data_as(_lib.c_vp), gr, gc, ptr(out),
+             count_bytes)
     return out, cell, count_bytes
 
 

@@ -125,6 +125,14 @@ SIGNATURES = {
     "ofr_olbp_hist": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp, c_int]),
     "ofr_lpq_codes": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp]),
     "ofr_lpq_hist": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_int]),
+    "ofr_elbp_codes_f": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int,
+                                 c_int, c_vp]),
+    "ofr_elbp_hist_f": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int,
+                                c_int, c_int, c_vp, c_int]),
+    "ofr_olbp_codes_f": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_vp]),
+    "ofr_olbp_hist_f": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_int, c_vp, c_int]),
+    "ofr_lpq_codes_f": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_vp, c_vp]),
+    "ofr_lpq_hist_f": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_int]),
     "ofr_tantriggs_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_dbl, c_dbl]),
     "ofr_tantriggs_f32": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_vp,
                                   c_sz]),

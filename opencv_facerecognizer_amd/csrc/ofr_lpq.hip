@@ -17,6 +17,8 @@
 // eight signs in registers.  Taps and V are kernel arguments (scalar loads).  The code of pixel (r, c) belongs at
 // linear index c*H + r of the [H][W] output (the reference flattens column-major and reshapes
 // row-major); the fused form counts it straight into LDS counters of the whole grid.
+// The kernel is typed on the pixel: float32 / float64 images (ofr_lpq_codes_f / ofr_lpq_hist_f) stage the
+// strip in their own width and run the same fp64 formulation.  (OriginalLBP on float images: ofr_lbp_float.hip.)
 #include <cmath>
 
 #include "ofr_common.h"
@@ -82,7 +84,11 @@ __global__ void __launch_bounds__(256) zero_kernel(uint32_t* __restrict__ p, int
     p[i] = 0;
 }
 
-__global__ void __launch_bounds__(THREADS) lpq_kernel(const uint8_t* __restrict__ imgs, Args a, void* __restrict__ out) {
+// T: the pixel type.  uint8_t is the byte path; float / double (ofr_lpq_*_f) stage the strip in their own
+// width -- the tile is copied as dwords either way -- and sum the w0 response in fp64 instead of uint32.
+template <typename T>
+__global__ void __launch_bounds__(THREADS) lpq_kernel(const T* __restrict__ imgs, Args a, void* __restrict__ out) {
+  constexpr bool BYTES = sizeof(T) == 1;
   const int R = a.R, N = 2 * R + 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int H = a.H, W = a.W, Wp = W + 2 * R, SR = a.SR;
@@ -91,10 +97,10 @@ __global__ void __launch_bounds__(THREADS) lpq_kernel(const uint8_t* __restrict_
   double* pl0 = reinterpret_cast<double*>(smem + (size_t)ncnt * 4);  // w0 sums   [SR][Wp]
   double* plr = pl0 + SR * Wp;                                       // Re w1 sums
   double* pli = plr + SR * Wp;                                       // Im w1 sums
-  uint8_t* tile = reinterpret_cast<uint8_t*>(pli + SR * Wp);         // [SR + 2R][W] bytes
+  T* tile = reinterpret_cast<T*>(pli + SR * Wp);                     // [SR + 2R][W] pixels
   const int64_t img = blockIdx.y;
   const int64_t npix = (int64_t)H * W;
-  const uint8_t* im = imgs + img * npix;
+  const T* im = imgs + img * npix;
   const int ncell = a.gr * a.gc;
   uint32_t* gcounts = reinterpret_cast<uint32_t*>((uint8_t*)out + img * (int64_t)ncell * 256 * a.count_bytes);
 
@@ -103,22 +109,24 @@ __global__ void __launch_bounds__(THREADS) lpq_kernel(const uint8_t* __restrict_
 
   const int nstrips = (H + SR - 1) / SR;
   const int s0 = blockIdx.x * a.strips_per_wg, s1 = min(nstrips, s0 + a.strips_per_wg);
-  const bool dwords = (W & 3) == 0 && ((uintptr_t)im & 3) == 0;
+  const bool dwords = ((W * (int)sizeof(T)) & 3) == 0 && ((uintptr_t)im & 3) == 0;
+  const uint8_t* imb = reinterpret_cast<const uint8_t*>(im);
+  const int64_t nbytes = npix * (int64_t)sizeof(T);
   for (int s = s0; s < s1; ++s) {
     const int y0 = s * SR, rows = min(SR, H - y0);
     __syncthreads();  // the previous strip's row pass is done with the planes
     // tile row t = image row y0 - R + t; rows are contiguous, so one flat copy, zero outside the image
-    const int tbytes = (rows + 2 * R) * W;
-    const int64_t off0 = (int64_t)(y0 - R) * W;
+    const int tbytes = (rows + 2 * R) * W * (int)sizeof(T);
+    const int64_t off0 = (int64_t)(y0 - R) * W * (int64_t)sizeof(T);
     if (dwords) {
       for (int i = threadIdx.x; i < tbytes / 4; i += THREADS) {
         const int64_t off = off0 + 4 * (int64_t)i;
-        reinterpret_cast<uint32_t*>(tile)[i] = (off >= 0 && off < npix) ? *reinterpret_cast<const uint32_t*>(im + off) : 0u;
+        reinterpret_cast<uint32_t*>(tile)[i] = (off >= 0 && off < nbytes) ? *reinterpret_cast<const uint32_t*>(imb + off) : 0u;
       }
     } else {
       for (int i = threadIdx.x; i < tbytes; i += THREADS) {
         const int64_t off = off0 + i;
-        tile[i] = (off >= 0 && off < npix) ? im[off] : (uint8_t)0;
+        reinterpret_cast<uint8_t*>(tile)[i] = (off >= 0 && off < nbytes) ? imb[off] : (uint8_t)0;
       }
     }
     __syncthreads();
@@ -128,9 +136,10 @@ __global__ void __launch_bounds__(THREADS) lpq_kernel(const uint8_t* __restrict_
     // PX pixels, and the planes' values are in flight for one tap pair only, not for the whole window.
     const int npx = rows * W;
     for (int i0 = threadIdx.x; i0 < npx; i0 += THREADS * PX) {
-      const uint8_t* col[PX];
+      const T* col[PX];
       int o[PX];
-      uint32_t sum[PX];
+      uint32_t sum[PX];   // w0 response of bytes: exact in integers
+      double sumd[PX];    // ... of float pixels
       double sr[PX], si[PX];
 #pragma unroll
       for (int p = 0; p < PX; ++p) {
@@ -139,23 +148,24 @@ __global__ void __launch_bounds__(THREADS) lpq_kernel(const uint8_t* __restrict_
         col[p] = tile + (yy + 2 * R) * W + x;
         o[p] = yy * Wp + x + R;
         sum[p] = 0;
-        sr[p] = si[p] = 0.0;
+        sumd[p] = sr[p] = si[p] = 0.0;
       }
 #pragma unroll 2
       for (int k = 0; k < N; ++k) {
         const double tr = a.tap[k][0], ti = a.tap[k][1];
 #pragma unroll
         for (int p = 0; p < PX; ++p) {
-          const uint32_t b = col[p][-k * W];
+          const T b = col[p][-k * W];
           const double v = (double)b;
-          sum[p] += b;
+          if constexpr (BYTES) sum[p] += b;
+          else sumd[p] += v;
           sr[p] += tr * v;
           si[p] += ti * v;
         }
       }
 #pragma unroll
       for (int p = 0; p < PX; ++p) {  // a clamped duplicate rewrites the last pixel's own values
-        pl0[o[p]] = (double)sum[p];
+        pl0[o[p]] = BYTES ? (double)sum[p] : sumd[p];
         plr[o[p]] = sr[p];
         pli[o[p]] = si[p];
       }
@@ -338,11 +348,12 @@ static int check_grid(const char* who, int dy, int dx, int gr, int gc, const voi
   return OFR_OK;
 }
 
-static int launch(hipStream_t st, const uint8_t* imgs, int64_t n, const Args& a, void* out, size_t lds,
+template <typename T>
+static int launch(hipStream_t st, const T* imgs, int64_t n, const Args& a, void* out, size_t lds,
                   size_t img_out_bytes) {
   static bool attr = false;
   if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)lpq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET);
+    hipError_t e = hipFuncSetAttribute((const void*)lpq_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET);
     if (e != hipSuccess) return hip_status(e, "hipFuncSetAttribute(lpq_kernel)");
     attr = true;
   }
@@ -350,21 +361,25 @@ static int launch(hipStream_t st, const uint8_t* imgs, int64_t n, const Args& a,
   const unsigned gx = (unsigned)cdiv(nstrips, a.strips_per_wg);
   for (int64_t done = 0; done < n; done += 65535) {
     const int64_t chunk = std::min<int64_t>(n - done, 65535);
-    hipLaunchKernelGGL(lpq_kernel, dim3(gx, (unsigned)chunk), dim3(THREADS), lds, st, imgs + done * (int64_t)a.H * a.W,
+    hipLaunchKernelGGL(lpq_kernel<T>, dim3(gx, (unsigned)chunk), dim3(THREADS), lds, st, imgs + done * (int64_t)a.H * a.W,
                        a, (void*)((char*)out + done * img_out_bytes));
     OFR_LAUNCH_CHECK("lpq_kernel");
   }
   return OFR_OK;
 }
 
-// codes (counts == false: out = uint8 [n][H][W]) or fused counts (out = [n][gr*gc][256])
-static int run(const char* who, void* stream, const uint8_t* imgs, int64_t n, int H, int W, int radius,
+// codes (counts == false: out = uint8 [n][H][W]) or fused counts (out = [n][gr*gc][256]); imgs are
+// pixels of pixel_bytes: 1 (uint8), 4 (float32) or 8 (float64)
+static int run(const char* who, void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W, int radius,
                const double* V_host, bool counts, int gr, int gc, void* out, int count_bytes) {
   const std::string w(who);
   if (n < 0 || H < 1 || W < 1) return fail(OFR_E_INVALID, w + ": bad sizes");
   if (radius < 1) return fail(OFR_E_INVALID, w + ": radius must be >= 1");
   if (radius > MAXR) return fail(OFR_E_UNSUPPORTED, w + ": radius must be <= 8");
   if (!V_host) return fail(OFR_E_INVALID, w + ": null basis");
+  if (pixel_bytes != 1 && pixel_bytes != 4 && pixel_bytes != 8)
+    return fail(OFR_E_INVALID, w + ": pixel_bytes must be 4 (float32) or 8 (float64)");
+  if ((uintptr_t)imgs % (uintptr_t)pixel_bytes) return fail(OFR_E_INVALID, w + ": images must be aligned to their pixels");
   Args a = {};
   a.H = H;
   a.W = W;
@@ -384,8 +399,8 @@ static int run(const char* who, void* stream, const uint8_t* imgs, int64_t n, in
   if (!imgs || !out) return fail(OFR_E_INVALID, w + ": null pointer");
   if ((int64_t)H * W > MAX_PIXELS) return fail(OFR_E_UNSUPPORTED, w + ": images above 2^22 pixels");
   // strip rows: what fits beside the counters; too few, and the counters move to global memory
-  const int64_t per_row = 3LL * (W + 2 * radius) * 8 + W;
-  const int64_t halo = 2LL * radius * W + 16;
+  const int64_t per_row = 3LL * (W + 2 * radius) * 8 + (int64_t)W * pixel_bytes;
+  const int64_t halo = 2LL * radius * W * pixel_bytes + 16;
   int64_t ncnt = counts ? (int64_t)gr * gc * 256 * 4 : 0;
   int64_t SR = (LDS_BUDGET - ncnt - halo) / per_row;
   if (counts && SR < std::min(H, 4)) {
@@ -420,7 +435,9 @@ static int run(const char* who, void* stream, const uint8_t* imgs, int64_t n, in
                        (uint32_t*)out, nwords);
     OFR_LAUNCH_CHECK("lpq zero_kernel");
   }
-  return launch(st, imgs, n, a, out, lds, img_out);
+  if (pixel_bytes == 4) return launch(st, (const float*)imgs, n, a, out, lds, img_out);
+  if (pixel_bytes == 8) return launch(st, (const double*)imgs, n, a, out, lds, img_out);
+  return launch(st, (const uint8_t*)imgs, n, a, out, lds, img_out);
 }
 
 }  // namespace lpq
@@ -431,12 +448,24 @@ using namespace ofr::lpq;
 
 extern "C" int ofr_lpq_codes(void* stream, const uint8_t* imgs, int64_t n, int H, int W, int radius,
                              const double* V_host, uint8_t* codes) {
-  return run("ofr_lpq_codes", stream, imgs, n, H, W, radius, V_host, false, 1, 1, codes, 1);
+  return run("ofr_lpq_codes", stream, imgs, 1, n, H, W, radius, V_host, false, 1, 1, codes, 1);
+}
+
+extern "C" int ofr_lpq_codes_f(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W, int radius,
+                               const double* V_host, uint8_t* codes) {
+  OFR_CHECK_ARG(pixel_bytes != 1, "ofr_lpq_codes_f: pixel_bytes must be 4 (float32) or 8 (float64)");
+  return run("ofr_lpq_codes_f", stream, imgs, pixel_bytes, n, H, W, radius, V_host, false, 1, 1, codes, 1);
 }
 
 extern "C" int ofr_lpq_hist(void* stream, const uint8_t* imgs, int64_t n, int H, int W, int radius,
                             const double* V_host, int gr, int gc, void* counts, int count_bytes) {
-  return run("ofr_lpq_hist", stream, imgs, n, H, W, radius, V_host, true, gr, gc, counts, count_bytes);
+  return run("ofr_lpq_hist", stream, imgs, 1, n, H, W, radius, V_host, true, gr, gc, counts, count_bytes);
+}
+
+extern "C" int ofr_lpq_hist_f(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W, int radius,
+                              const double* V_host, int gr, int gc, void* counts, int count_bytes) {
+  OFR_CHECK_ARG(pixel_bytes != 1, "ofr_lpq_hist_f: pixel_bytes must be 4 (float32) or 8 (float64)");
+  return run("ofr_lpq_hist_f", stream, imgs, pixel_bytes, n, H, W, radius, V_host, true, gr, gc, counts, count_bytes);
 }
 
 extern "C" int ofr_olbp_codes(void* stream, const uint8_t* imgs, int64_t n, int H, int W, uint8_t* codes) {

@@ -574,7 +574,14 @@ class SpatialHistogram(AbstractFeature):
     which is exactly what numpy's ``np.histogram(..., density=True)`` gives for one cell
     (feature.py:298-299).  ``compute`` leaves the device counts for the classifier
     (``PredictableModel.compute``): the LBPH gallery stays resident as counts, never rebuilt from
-    the float64 list."""
+    the float64 list.
+
+    Images: 8-bit grey images, or float32 / float64 images of arbitrary values (the float kernels, see
+    lbp.py) -- host lists and arrays, or uint8 / float32 / float64 device tensors [n][H][W] such as
+    ``ingest.faces`` and ``preprocessing.extract_batch`` return.  A device tensor stays on the device;
+    one of any other dtype is a TypeError."""
+
+    device_batches = True     # compute / counts_batch take a device face batch (ChainOperator.compute)
 
     def __init__(self, lbp_operator=ExtendedLBP(), sz=(8, 8)):
         AbstractFeature.__init__(self)
@@ -596,15 +603,16 @@ class SpatialHistogram(AbstractFeature):
         return self.histograms([X])[0]
 
     def counts_device(self, imgs):
-        """uint8 image stack (n,H,W) (host or device) -> (counts device tensor [n][cells][2^P], cell pixels, bytes)."""
+        """Image stack (n,H,W), host or device, uint8 / float32 / float64 -> (counts device tensor
+        [n][cells][2^P], cell pixels, bytes)."""
         op = self.lbp_operator
         if not isinstance(op, (ExtendedLBP, OriginalLBP, LPQ)):
             raise NotImplementedError("SpatialHistogram (MI355X build) runs ExtendedLBP, OriginalLBP and LPQ operators only")
-        from .lbp import as_u8_images
+        from .lbp import as_pixel_images
         if not hasattr(imgs, "device"):
-            imgs = as_u8_images(np.ascontiguousarray(imgs) if isinstance(imgs, np.ndarray) and imgs.ndim == 3
-                                else np.stack([np.asarray(x) for x in imgs]))
-        imgs = _device.u8_images(imgs)
+            imgs = as_pixel_images(np.ascontiguousarray(imgs) if isinstance(imgs, np.ndarray) and imgs.ndim == 3
+                                   else np.stack([np.asarray(x) for x in imgs]))
+        imgs = _device.pixel_images(imgs)
         if isinstance(op, LPQ):
             return _device.lpq_hist(imgs, int(op.radius), op.basis(), tuple(self.sz))
         if isinstance(op, OriginalLBP):
@@ -612,9 +620,9 @@ class SpatialHistogram(AbstractFeature):
         return _device.elbp_hist(imgs, op.geometry(), tuple(self.sz))
 
     def counts_batch(self, X):
-        """Faces of one size (list, array [n][H][W] or a uint8 device tensor such as ``ingest.faces``
-        returns) -> (counts [n][cells * 2^P] device tensor, cell pixel count, bytes per count), one
-        launch.  The histogram of face i is counts[i] / cell."""
+        """Faces of one size (list, array [n][H][W] or a uint8 / float32 / float64 device tensor such as
+        ``ingest.faces`` or ``preprocessing.extract_batch`` returns) -> (counts [n][cells * 2^P] device
+        tensor, cell pixel count, bytes per count), one launch.  The histogram of face i is counts[i] / cell."""
         counts, cell, cb = self.counts_device(X if hasattr(X, "device") or (isinstance(X, np.ndarray) and X.ndim == 3)
                                               else list(X))
         return counts.reshape(counts.shape[0], -1), cell, cb
@@ -624,16 +632,15 @@ class SpatialHistogram(AbstractFeature):
         return self._histograms(X)[0]
 
     def _histograms(self, X, keep_device=False):
-        if hasattr(X, "device"):          # a device face batch [n][H][W]
-            X = X.cpu().numpy()
         if len(X) == 0:
             return [], None
-        shapes = {np.asarray(x).shape for x in X}
+        on_device = hasattr(X, "device")  # a device face batch [n][H][W]: one size, no host trip
+        shapes = {None} if on_device else {np.asarray(x).shape for x in X}
         out = [None] * len(X)
         dev = None
         for shp in shapes:   # images of one size per launch
-            sel = [i for i, x in enumerate(X) if np.asarray(x).shape == shp]
-            counts, cell, cb = self.counts_device([X[i] for i in sel])
+            sel = list(range(len(X))) if on_device else [i for i, x in enumerate(X) if np.asarray(x).shape == shp]
+            counts, cell, cb = self.counts_device(X if on_device else [X[i] for i in sel])
             c = _device.counts_numpy(counts, cb).astype(np.int64).reshape(len(sel), -1)
             with np.errstate(invalid="ignore", divide="ignore"):
                 h = c.astype(np.float64) / float(cell)

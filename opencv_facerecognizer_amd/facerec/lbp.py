@@ -14,7 +14,21 @@ bit-exact.  LPQ runs in fp64 with the decorrelation matrix ``V`` derived on
 the host (``LPQ.basis``) and agrees with the reference wherever the
 decorrelated responses are above rounding noise (on a window of
 constant grey every response is zero up to noise and the reference's own code
-is the sign of that noise).  All three take 8-bit grey images.
+is the sign of that noise).
+
+Images.  8-bit grey images -- uint8, or any array whose values are integers in
+0..255 -- take the byte kernels.  2-D float32 / float64 images of arbitrary
+values (what ``TanTriggsPreprocessing`` and ``HistogramEqualization`` return)
+take the float kernels (``ofr_*_f``, ofr_lbp_float.hip): every pixel is
+converted exactly to float64 and all arithmetic is float64, which is what the
+installed numpy 2.x does with the reference on a float image.  One quirk of the
+reference is kept, not fixed: ExtendedLBP's centre is
+``np.asarray(X[...], dtype=np.uint8)`` (lbp.py:104), i.e.
+``C = trunc(x).astype(int64) & 255`` -- floor for 0 <= x < 256 and wrap-around
+outside it (-3.7 -> 253, 300.7 -> 44), so the negative half of a Tan-Triggs face
+has centres near 255.  OriginalLBP compares the values as given.  Codes touching
+a non-finite pixel (a constant face under Tan-Triggs is 0/0) are unspecified;
+they stay inside the histogram range.
 
 Out of scope: VarLBP (lbp.py:140-208) — its values are real variances that
 mostly fall outside the histogram range.
@@ -79,6 +93,26 @@ def as_u8_images(X):
     raise NotImplementedError("the LBP operators (MI355X build) accept 8-bit grey images (integer values 0..255)")
 
 
+def as_pixel_images(X):
+    """Image or stack of images -> what the kernels take: uint8 where ``as_u8_images`` gives it (the byte
+    kernels), float32 / float64 arrays of any other values as they are (the float kernels)."""
+    X = np.asanyarray(X)
+    if X.dtype in (np.float32, np.float64):
+        with np.errstate(invalid="ignore"):     # NaN / out-of-range values: not integer-valued
+            Xi = X.astype(np.uint8)
+            return Xi if np.array_equal(Xi.astype(X.dtype), X) else np.asarray(X)
+    return as_u8_images(X)
+
+
+def _device_image(X, who):
+    """One 2-D image -> device stack [1][H][W] of its kernel dtype."""
+    from .. import _device
+    X = as_pixel_images(X)
+    if X.ndim != 2:
+        raise ValueError("%s expects a 2-D image" % who)
+    return _device.pixel_images(X[None])
+
+
 class ExtendedLBP(LocalDescriptor):
     """lbp.py:75-137 on the GPU."""
 
@@ -91,16 +125,13 @@ class ExtendedLBP(LocalDescriptor):
 
     def __call__(self, X):
         from .. import _device
-        X = as_u8_images(X)
-        if X.ndim != 2:
-            raise ValueError("ExtendedLBP expects a 2-D image")
-        codes = _device.elbp_codes(_device.u8_images(X[None]), self.geometry())
+        codes = _device.elbp_codes(_device_image(X, "ExtendedLBP"), self.geometry())
         return codes.cpu().numpy()[0].view(np.uint32)
 
     def codes_batch(self, imgs_u8_device):
-        """uint8 [n][H][W] device tensor -> int32-stored uint32 codes [n][dy][dx] (device)."""
+        """uint8, float32 or float64 [n][H][W] device tensor -> int32-stored uint32 codes [n][dy][dx] (device)."""
         from .. import _device
-        return _device.elbp_codes(imgs_u8_device, self.geometry())
+        return _device.elbp_codes(_device.pixel_images(imgs_u8_device), self.geometry())
 
     @property
     def radius(self):
@@ -118,10 +149,7 @@ class OriginalLBP(LocalDescriptor):
 
     def __call__(self, X):
         from .. import _device
-        X = as_u8_images(X)
-        if X.ndim != 2:
-            raise ValueError("OriginalLBP expects a 2-D image")
-        return _device.olbp_codes(_device.u8_images(X[None])).cpu().numpy()[0].astype(np.int64)
+        return _device.olbp_codes(_device_image(X, "OriginalLBP")).cpu().numpy()[0].astype(np.int64)
 
     def __repr__(self):
         return "OriginalLBP (neighbors=%s)" % (self._neighbors)
@@ -187,10 +215,7 @@ class LPQ(LocalDescriptor):
 
     def __call__(self, X):
         from .. import _device
-        X = as_u8_images(X)
-        if X.ndim != 2:
-            raise ValueError("LPQ expects a 2-D image")
-        codes = _device.lpq_codes(_device.u8_images(X[None]), int(self._radius), self.basis())
+        codes = _device.lpq_codes(_device_image(X, "LPQ"), int(self._radius), self.basis())
         return codes.cpu().numpy()[0].astype(np.int64)
 
     @property

@@ -11,7 +11,10 @@ features never leave the GPU:
   distance.py:101-183): ONE histogram launch per batch (``ofr_elbp_hist``,
   ``ofr_olbp_hist`` or ``ofr_lpq_hist``) gives the
   integer cell histograms, searched as counts against the counts gallery
-  ``compute`` left on the device (``ofr_chi2_knn`` / ``ofr_hist_knn``);
+  ``compute`` left on the device (``ofr_chi2_knn`` / ``ofr_hist_knn``).  The same with
+  TanTriggsPreprocessing or HistogramEqualization chained in front (``ChainOperator``): one
+  preprocessing launch, whose float faces go to the float histogram kernels (``ofr_*_hist_f``) on
+  the device, then the counts search;
 * ChainOperator(TanTriggsPreprocessing | HistogramEqualization, Fisherfaces) +
   NearestNeighbor (Euclidean/Cosine): one preprocessing launch
   (``ofr_tantriggs_f32`` / ``ofr_histeq_f64``), one fp64 projection with the
@@ -43,7 +46,8 @@ class PredictableModel(object):
         builds its device gallery from them (no host round trip of the gallery)."""
         features = self.feature.compute(X, y)
         self.classifier.compute(features, y)
-        dev = self.feature.__dict__.pop("_dev_features", None)
+        holder = self.feature.model2 if self._lbph_chain() else self.feature   # who left device features
+        dev = holder.__dict__.pop("_dev_features", None)
         if dev is None or dev[0] != id(features):
             return
         if isinstance(dev[1], tuple) and dev[1][0] == "counts":       # SpatialHistogram counts
@@ -61,7 +65,7 @@ class PredictableModel(object):
 
     def predict(self, X):
         """model.py:53-55 (one face)."""
-        if self._chain():     # one face: the reference's own order, extract then classify
+        if self._chain() or self._lbph_chain():     # one face: the reference's own order, extract then classify
             return self.classifier.predict(self.feature.extract(X))
         return self.predict_batch([X])[0]
 
@@ -80,8 +84,18 @@ class PredictableModel(object):
                 and isinstance(f.model2, Fisherfaces) and type(self.classifier) is NearestNeighbor
                 and getattr(self.classifier.dist_metric, "metric_id", None) in (0, 1))
 
+    def _lbph_chain(self):
+        """ChainOperator(TanTriggsPreprocessing | HistogramEqualization, SpatialHistogram): the LBPH route
+        with one preprocessing launch in front."""
+        f = self.feature
+        return (type(f) is ChainOperator and type(f.model1) in (TanTriggsPreprocessing, HistogramEqualization)
+                and type(f.model2) is SpatialHistogram and self._lbph())
+
     def _lbph(self):
-        return (type(self.feature) is SpatialHistogram and isinstance(self.feature.lbp_operator, (ExtendedLBP, OriginalLBP, LPQ))
+        f = self.feature
+        if type(f) is ChainOperator and type(f.model1) in (TanTriggsPreprocessing, HistogramEqualization):
+            f = f.model2
+        return (type(f) is SpatialHistogram and isinstance(f.lbp_operator, (ExtendedLBP, OriginalLBP, LPQ))
                 and type(self.classifier) is NearestNeighbor
                 and getattr(self.classifier.dist_metric, "metric_id", None) in _lib.HIST_METRICS)
 
@@ -102,8 +116,16 @@ class PredictableModel(object):
         return clf._search_prepared(Qd, k)
 
     def _search_lbph(self, X, k):
-        """LBPH batch: faces grouped by size, one histogram launch + one counts search per group."""
+        """LBPH batch: faces grouped by size, one histogram launch + one counts search per group (behind a
+        preprocessing step: its launch first, the float faces stay on the device)."""
         import torch
+        if self._lbph_chain():
+            pre, sh = self.feature.model1, self.feature.model2
+
+            def counts_batch(xs):
+                return sh.counts_batch(pre.extract_batch(xs))
+        else:
+            counts_batch = self.feature.counts_batch
         if hasattr(X, "device") or (isinstance(X, np.ndarray) and X.ndim == 3):   # one face size
             groups = [(None, X)]
         else:
@@ -113,7 +135,7 @@ class PredictableModel(object):
                 shapes.setdefault(np.asarray(x).shape, []).append(i)
             groups = [(sel, [X[i] for i in sel]) for sel in shapes.values()]
         if len(groups) == 1:
-            C, cell, cb = self.feature.counts_batch(groups[0][1])
+            C, cell, cb = counts_batch(groups[0][1])
             return self.classifier.search_counts(C, cell, cb, k)
         # a group whose cell size differs from the counts gallery's comes back on the host
         # (search_counts' float path): every group's result goes to the gallery device
@@ -121,7 +143,7 @@ class PredictableModel(object):
         dev = _lib.device()
         d_all = i_all = None
         for sel, xs in groups:
-            C, cell, cb = self.feature.counts_batch(xs)
+            C, cell, cb = counts_batch(xs)
             d, i = self.classifier.search_counts(C, cell, cb, k)
             if d_all is None:
                 d_all = torch.empty((B,) + tuple(d.shape[1:]), dtype=d.dtype, device=dev)

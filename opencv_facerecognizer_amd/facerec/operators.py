@@ -23,12 +23,19 @@ class FeatureOperator(AbstractFeature):
 
 
 class ChainOperator(FeatureOperator):
-    """operators.py:58-81: model2.compute(model1.compute(X, y), y)."""
+    """operators.py:58-81: model2.compute(model1.compute(X, y), y).  A model1 with ``compute_device`` (the
+    preprocessing kernels) in front of a model2 that takes device batches (``device_batches``:
+    SpatialHistogram) keeps training faces of one size on the device between the two."""
 
     def __init__(self, model1, model2):
         FeatureOperator.__init__(self, model1, model2)
 
     def compute(self, X, y):
+        dev1 = getattr(self.model1, "compute_device", None)
+        if dev1 is not None and getattr(self.model2, "device_batches", False):
+            Xd = dev1(X, y)
+            if Xd is not None:
+                return self.model2.compute(Xd, y)
         X = self.model1.compute(X, y)
         return self.model2.compute(X, y)
 

@@ -8,8 +8,9 @@ Their arithmetic runs in ``ofr_tantriggs_f32`` / ``ofr_histeq_f64``
 ``extract`` handles one face, and ``extract_batch`` (new) takes a list, an array
 ``[n][H][W]`` or a uint8 device tensor and leaves the result on the device, where
 ``Fisherfaces.project_device`` consumes it (``ChainOperator.extract_batch``,
-``PredictableModel.predict_batch``).  Both take 8-bit grey images (``as_u8_images``,
-as the LBP operators do).
+``PredictableModel.predict_batch``) and so do ``SpatialHistogram.counts_batch`` and
+``compute`` (the LBPH route; the LBP kernels take float faces).  Both take 8-bit grey
+images (``as_u8_images``).
 
 Tan-Triggs returns float32 like the reference; its filter accumulates in fp64,
 so it sits closer to the exact result than the reference's own float32 run
@@ -52,6 +53,16 @@ class _DevicePreprocessing(AbstractFeature):
         if not (isinstance(X, np.ndarray) and X.ndim == 3):
             X = np.stack([np.asarray(x) for x in X])
         return self._run(_device.u8_images(as_u8_images(X)))
+
+    def compute_device(self, X, y):
+        """``compute`` for a consumer on the device (``ChainOperator.compute``): faces of one size -> device
+        tensor [n][H][W], one launch; None for mixed sizes or no faces (the caller takes ``compute``)."""
+        if hasattr(X, "data_ptr") or (isinstance(X, np.ndarray) and X.ndim == 3):
+            return self.extract_batch(X) if len(X) else None
+        X = [np.asarray(x) for x in X]
+        if not X or any(x.shape != X[0].shape for x in X):
+            return None
+        return self.extract_batch(X)
 
     def compute(self, X, y):
         if hasattr(X, "data_ptr"):
@@ -110,7 +121,9 @@ class TanTriggsPreprocessing(_DevicePreprocessing):
 
 
 class LBPPreprocessing(AbstractFeature):
-    """preprocessing.py:112-127: the LBP code image of each face."""
+    """preprocessing.py:112-127: the LBP code image of each face.  The operators take float images
+    (lbp.py), so this class also works behind ``TanTriggsPreprocessing`` / ``HistogramEqualization`` in a
+    ``ChainOperator``, with no code of its own for that."""
 
     def __init__(self, lbp_operator=ExtendedLBP(radius=1, neighbors=8)):
         AbstractFeature.__init__(self)
