@@ -507,6 +507,41 @@ int ofr_tantriggs_f32(void* stream, const uint8_t* imgs, int64_t n, int H, int W
 int ofr_histeq_f64(void* stream, const uint8_t* imgs, int64_t n, int H, int W, int num_bins,
                    double* out);
 
+/* The same two steps on float images (ofr_preproc_float.hip) -------------------
+ * imgs: float32 (pixel_bytes 4) or float64 (pixel_bytes 8) [n][H][W] contiguous,
+ * aligned to the pixel; any other pixel_bytes is OFR_E_INVALID.  Arguments,
+ * limits, error codes and messages otherwise as for the byte entry points; all
+ * argument checks come before any device work.
+ * ofr_tantriggs_f32_f: every pixel is rounded once to float32 (the reference's
+ * np.array(X, dtype=np.float32)), X = v^gamma per pixel (no table: fp64
+ * exp2(gamma log2 v) rounded once to fp32), then exactly the arithmetic of
+ * ofr_tantriggs_f32: fp64 taps, fma accumulation in fp64, one fp32 rounding
+ * between the two filter passes, fixed-order reductions.  A face is done in one
+ * launch up to 113 x 113 at the default sigmas (fp32 strip plane: 12 bytes per
+ * pixel of LDS), larger ones in row strips.  The strip count differs from the
+ * byte kernel's, so the workspace size comes from
+ * ofr_tantriggs_workspace_bytes_f, never from ofr_tantriggs_workspace_bytes.
+ * A negative pixel is NaN^gamma in the reference: the face's values are
+ * unspecified here, nothing traps or is written out of range.  A constant face
+ * is 0/0 as above.
+ * ofr_histeq_f64_f: np.histogram / np.interp as numpy 2.x evaluates them on an
+ * array of the image's dtype.  float32: min / max, the +-0.5 widening, the
+ * np.linspace edges (i * step + first, the last one exact), the index (subtract,
+ * divide by the range, multiply by num_bins, truncate, fold == num_bins, one
+ * decrement / increment against the edges) and np.diff of the edges are all
+ * float32; float64: all fp64.  Density, cumulative sum, 255 cdf / cdf[-1] and
+ * np.interp are fp64 for both.  A non-finite pixel (numpy raises) or a range
+ * whose step underflows to zero leaves the face's values unspecified; nothing
+ * traps.  The face stays in LDS between the counting and the output read when
+ * it fits 160 KiB with the tables, else it is read from memory three times.
+ * No time of either kernel has been measured.                                  */
+size_t ofr_tantriggs_workspace_bytes_f(int64_t n, int H, int W, double sigma0, double sigma1);
+int ofr_tantriggs_f32_f(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W,
+                        double alpha, double tau, double gamma, double sigma0, double sigma1,
+                        float* out, void* workspace, size_t workspace_bytes);
+int ofr_histeq_f64_f(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W,
+                     int num_bins, double* out);
+
 /* Chi-square search ----------------------------------------------------------
  * Replaces ChiSquareDistance distance.py:112-116 inside NearestNeighbor.predict.
  * Q [B][ldq], G [N][ldg] rows of `nbins` values of type dtype (OFR_DT_*); the

@@ -1401,33 +1401,46 @@ def lpq_hist(imgs_u8, radius, V, grid, count_bytes=None):
 # ---------------------------------------------------------------------------
 # preprocessing  (preprocessing.py:73-77, 98-105)
 # ---------------------------------------------------------------------------
-def _u8_batch(imgs_u8):
-    if imgs_u8.dtype != torch.uint8 or imgs_u8.dim() != 3:
-        raise TypeError("expected a uint8 device tensor [n][H][W]")
-    return imgs_u8.contiguous()
+def _pixel_batch(imgs):
+    if imgs.dim() != 3:
+        raise TypeError("expected a device tensor [n][H][W]")
+    if imgs.dtype not in _PIXEL_DTYPES:
+        raise TypeError("preprocessing images must be uint8, float32 or float64, got %s" % imgs.dtype)
+    return imgs.contiguous()
 
 
-def tantriggs(imgs_u8, alpha=0.1, tau=10.0, gamma=0.2, sigma0=1.0, sigma1=2.0):
-    """Tan-Triggs normalisation (preprocessing.py:98-105): uint8 [n][H][W] device tensor -> float32 [n][H][W].
-    One launch per batch for faces that fit a workgroup's LDS (128 x 128 does), three for larger ones; a
-    face's result does not depend on its batch.  A constant face is 0/0 as in the reference: NaN."""
-    imgs_u8 = _u8_batch(imgs_u8)
-    n, H, W = imgs_u8.shape
-    out = torch.empty((n, H, W), dtype=torch.float32, device=imgs_u8.device)
-    nbytes = _lib.load().ofr_tantriggs_workspace_bytes(n, H, W, float(sigma0), float(sigma1))
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=imgs_u8.device) if nbytes else None
-    call("ofr_tantriggs_f32", stream(), ptr(imgs_u8), n, H, W, float(alpha), float(tau), float(gamma), float(sigma0),
-         float(sigma1), ptr(out), ptr(ws), nbytes)
+def tantriggs(imgs, alpha=0.1, tau=10.0, gamma=0.2, sigma0=1.0, sigma1=2.0):
+    """Tan-Triggs normalisation (preprocessing.py:98-105): uint8, float32 or float64 [n][H][W] device tensor ->
+    float32 [n][H][W].  One launch per batch for faces that fit a workgroup's LDS (uint8: 128 x 128 does;
+    float: 113 x 113), three for larger ones; a face's result does not depend on its batch.  A constant face
+    is 0/0 as in the reference: NaN."""
+    imgs = _pixel_batch(imgs)
+    n, H, W = imgs.shape
+    pb = _pixel_bytes(imgs)
+    out = torch.empty((n, H, W), dtype=torch.float32, device=imgs.device)
+    size = _lib.load().ofr_tantriggs_workspace_bytes_f if pb else _lib.load().ofr_tantriggs_workspace_bytes
+    nbytes = size(n, H, W, float(sigma0), float(sigma1))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=imgs.device) if nbytes else None
+    params = (float(alpha), float(tau), float(gamma), float(sigma0), float(sigma1), ptr(out), ptr(ws), nbytes)
+    if pb:
+        call("ofr_tantriggs_f32_f", stream(), ptr(imgs), pb, n, H, W, *params)
+    else:
+        call("ofr_tantriggs_f32", stream(), ptr(imgs), n, H, W, *params)
     return out
 
 
-def histeq(imgs_u8, num_bins=256):
-    """Histogram equalisation (preprocessing.py:73-77, np.histogram(density=True) + np.interp): uint8 [n][H][W]
-    device tensor -> float64 [n][H][W] in 0..255, one launch."""
-    imgs_u8 = _u8_batch(imgs_u8)
-    n, H, W = imgs_u8.shape
-    out = torch.empty((n, H, W), dtype=torch.float64, device=imgs_u8.device)
-    call("ofr_histeq_f64", stream(), ptr(imgs_u8), n, H, W, int(num_bins), ptr(out))
+def histeq(imgs, num_bins=256):
+    """Histogram equalisation (preprocessing.py:73-77, np.histogram(density=True) + np.interp on an array of the
+    images' dtype): uint8, float32 or float64 [n][H][W] device tensor -> float64 [n][H][W] in 0..255, one
+    launch."""
+    imgs = _pixel_batch(imgs)
+    n, H, W = imgs.shape
+    pb = _pixel_bytes(imgs)
+    out = torch.empty((n, H, W), dtype=torch.float64, device=imgs.device)
+    if pb:
+        call("ofr_histeq_f64_f", stream(), ptr(imgs), pb, n, H, W, int(num_bins), ptr(out))
+    else:
+        call("ofr_histeq_f64", stream(), ptr(imgs), n, H, W, int(num_bins), ptr(out))
     return out
 
 

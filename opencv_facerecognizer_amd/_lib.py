@@ -137,6 +137,10 @@ SIGNATURES = {
     "ofr_tantriggs_f32": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_vp,
                                   c_sz]),
     "ofr_histeq_f64": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp]),
+    "ofr_tantriggs_workspace_bytes_f": (c_sz, [c_i64, c_int, c_int, c_dbl, c_dbl]),
+    "ofr_tantriggs_f32_f": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp,
+                                    c_vp, c_sz]),
+    "ofr_histeq_f64_f": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_vp]),
     "ofr_chi2_workspace_bytes": (c_sz, [c_i64, c_i64, c_int]),
     "ofr_chi2_mfma_bound": (c_dbl, [c_i64]),
     "ofr_chi2_table": (None, [c_vp]),

@@ -12,13 +12,13 @@ features never leave the GPU:
   ``ofr_olbp_hist`` or ``ofr_lpq_hist``) gives the
   integer cell histograms, searched as counts against the counts gallery
   ``compute`` left on the device (``ofr_chi2_knn`` / ``ofr_hist_knn``).  The same with
-  TanTriggsPreprocessing or HistogramEqualization chained in front (``ChainOperator``): one
-  preprocessing launch, whose float faces go to the float histogram kernels (``ofr_*_hist_f``) on
-  the device, then the counts search;
-* ChainOperator(TanTriggsPreprocessing | HistogramEqualization, Fisherfaces) +
-  NearestNeighbor (Euclidean/Cosine): one preprocessing launch
-  (``ofr_tantriggs_f32`` / ``ofr_histeq_f64``), one fp64 projection with the
-  gallery centring folded in, one search.
+  preprocessing chained in front (``ChainOperator``; TanTriggsPreprocessing, HistogramEqualization or
+  a ChainOperator of them at any depth): one launch per preprocessing step, whose float faces go to
+  the next step's float kernel and to the float histogram kernels (``ofr_*_hist_f``) on the device,
+  then the counts search;
+* ChainOperator(preprocessing as above, Fisherfaces) + NearestNeighbor (Euclidean/Cosine): the
+  preprocessing launches (``ofr_tantriggs_f32`` / ``ofr_histeq_f64`` and their ``_f`` twins for
+  float faces), one fp64 projection with the gallery centring folded in, one search.
 """
 from __future__ import annotations
 
@@ -30,6 +30,18 @@ from .feature import AbstractFeature, Fisherfaces, SpatialHistogram
 from .lbp import LPQ, ExtendedLBP, OriginalLBP
 from .operators import ChainOperator
 from .preprocessing import HistogramEqualization, TanTriggsPreprocessing
+
+
+def _preprocessing(f):
+    """TanTriggsPreprocessing, HistogramEqualization, or a ChainOperator of them at any depth."""
+    if type(f) is ChainOperator:
+        return _preprocessing(f.model1) and _preprocessing(f.model2)
+    return type(f) in (TanTriggsPreprocessing, HistogramEqualization)
+
+
+def _preprocessed(f):
+    """ChainOperator(preprocessing, feature): the device routes run model1's launches in front of model2."""
+    return type(f) is ChainOperator and _preprocessing(f.model1)
 
 
 class PredictableModel(object):
@@ -80,20 +92,20 @@ class PredictableModel(object):
 
     def _chain(self):
         f = self.feature
-        return (type(f) is ChainOperator and type(f.model1) in (TanTriggsPreprocessing, HistogramEqualization)
+        return (_preprocessed(f)
                 and isinstance(f.model2, Fisherfaces) and type(self.classifier) is NearestNeighbor
                 and getattr(self.classifier.dist_metric, "metric_id", None) in (0, 1))
 
     def _lbph_chain(self):
-        """ChainOperator(TanTriggsPreprocessing | HistogramEqualization, SpatialHistogram): the LBPH route
-        with one preprocessing launch in front."""
+        """ChainOperator(preprocessing, SpatialHistogram): the LBPH route with the preprocessing launches in
+        front."""
         f = self.feature
-        return (type(f) is ChainOperator and type(f.model1) in (TanTriggsPreprocessing, HistogramEqualization)
+        return (_preprocessed(f)
                 and type(f.model2) is SpatialHistogram and self._lbph())
 
     def _lbph(self):
         f = self.feature
-        if type(f) is ChainOperator and type(f.model1) in (TanTriggsPreprocessing, HistogramEqualization):
+        if _preprocessed(f):
             f = f.model2
         return (type(f) is SpatialHistogram and isinstance(f.lbp_operator, (ExtendedLBP, OriginalLBP, LPQ))
                 and type(self.classifier) is NearestNeighbor

@@ -25,10 +25,28 @@ class FeatureOperator(AbstractFeature):
 class ChainOperator(FeatureOperator):
     """operators.py:58-81: model2.compute(model1.compute(X, y), y).  A model1 with ``compute_device`` (the
     preprocessing kernels) in front of a model2 that takes device batches (``device_batches``:
-    SpatialHistogram) keeps training faces of one size on the device between the two."""
+    SpatialHistogram, the preprocessing steps) keeps training faces of one size on the device between the
+    two.  A chain offers the same two hooks itself -- ``compute_device`` when both members have it,
+    ``device_batches`` when model2 has it -- so a nested chain of preprocessing steps stays on the device."""
 
     def __init__(self, model1, model2):
         FeatureOperator.__init__(self, model1, model2)
+
+    @property
+    def compute_device(self):
+        dev1 = getattr(self.model1, "compute_device", None)
+        dev2 = getattr(self.model2, "compute_device", None)
+        if dev1 is None or dev2 is None:
+            raise AttributeError("compute_device")
+
+        def run(X, y):
+            Xd = dev1(X, y)
+            return None if Xd is None else dev2(Xd, y)
+        return run
+
+    @property
+    def device_batches(self):
+        return getattr(self.model2, "device_batches", False)
 
     def compute(self, X, y):
         dev1 = getattr(self.model1, "compute_device", None)

@@ -4,13 +4,19 @@
 (preprocessing.py:62-80) keep their constructor arguments, ``repr`` and pickled
 state (``_alpha``, ``_tau``, ``_gamma``, ``_sigma0``, ``_sigma1`` / ``_num_bins``).
 Their arithmetic runs in ``ofr_tantriggs_f32`` / ``ofr_histeq_f64``
-(ofr_preproc.hip): ``compute`` makes one launch per group of same-sized faces,
-``extract`` handles one face, and ``extract_batch`` (new) takes a list, an array
-``[n][H][W]`` or a uint8 device tensor and leaves the result on the device, where
-``Fisherfaces.project_device`` consumes it (``ChainOperator.extract_batch``,
-``PredictableModel.predict_batch``) and so do ``SpatialHistogram.counts_batch`` and
-``compute`` (the LBPH route; the LBP kernels take float faces).  Both take 8-bit grey
-images (``as_u8_images``).
+(ofr_preproc.hip, 8-bit faces) and ``ofr_tantriggs_f32_f`` / ``ofr_histeq_f64_f``
+(ofr_preproc_float.hip, float32 / float64 faces): ``compute`` makes one launch per
+group of same-sized faces, ``extract`` handles one face, and ``extract_batch`` (new)
+takes a list, an array ``[n][H][W]`` or a uint8 / float32 / float64 device tensor and
+leaves the result on the device, where the other preprocessing step,
+``Fisherfaces.project_device`` (``ChainOperator.extract_batch``,
+``PredictableModel.predict_batch``), ``SpatialHistogram.counts_batch`` and ``compute``
+(the LBPH route; the LBP kernels take float faces) consume it.  Host input goes
+through ``lbp.as_pixel_images``: integer-valued faces of any dtype keep the byte
+kernels, any other float32 / float64 face takes the float kernels -- so
+``ChainOperator(TanTriggsPreprocessing(), HistogramEqualization())`` (and the other
+order) works as in the reference, on the device from end to end.  Any other device
+dtype is a ``TypeError``.
 
 Tan-Triggs returns float32 like the reference; its filter accumulates in fp64,
 so it sits closer to the exact result than the reference's own float32 run
@@ -33,26 +39,30 @@ import numpy as np
 import torch
 
 from .feature import AbstractFeature
-from .lbp import ExtendedLBP, as_u8_images
+from .lbp import ExtendedLBP, as_pixel_images
 
 
 class _DevicePreprocessing(AbstractFeature):
-    """Batch plumbing shared by the two kernels; a subclass supplies ``_run(uint8 device [n][H][W])``."""
+    """Batch plumbing shared by the kernels; a subclass supplies ``_run(device [n][H][W])`` for uint8,
+    float32 and float64 pixels."""
 
-    def _run(self, imgs_u8):
+    device_batches = True     # compute takes a device face batch (ChainOperator.compute)
+
+    def _run(self, imgs):
         raise NotImplementedError
 
     def extract_batch(self, X):
-        """Faces of one size (list, array [n][H][W] or a uint8 device tensor [n][H][W], e.g. from
-        ``ingest.faces``) -> device tensor [n][H][W], one launch."""
+        """Faces of one size (list, array [n][H][W] or a uint8 / float32 / float64 device tensor [n][H][W],
+        e.g. from ``ingest.faces`` or from another preprocessing step) -> device tensor [n][H][W], one
+        launch."""
         from .. import _device
         if hasattr(X, "data_ptr"):
-            if X.dtype != torch.uint8:
-                raise TypeError("device face batches must be uint8")
+            if X.dtype not in (torch.uint8, torch.float32, torch.float64):
+                raise TypeError("device face batches must be uint8, float32 or float64")
             return self._run(X)
         if not (isinstance(X, np.ndarray) and X.ndim == 3):
             X = np.stack([np.asarray(x) for x in X])
-        return self._run(_device.u8_images(as_u8_images(X)))
+        return self._run(_device.pixel_images(as_pixel_images(X)))
 
     def compute_device(self, X, y):
         """``compute`` for a consumer on the device (``ChainOperator.compute``): faces of one size -> device
@@ -92,9 +102,9 @@ class HistogramEqualization(_DevicePreprocessing):
         AbstractFeature.__init__(self)
         self._num_bins = num_bins
 
-    def _run(self, imgs_u8):
+    def _run(self, imgs):
         from .. import _device
-        return _device.histeq(imgs_u8, int(self._num_bins))
+        return _device.histeq(imgs, int(self._num_bins))
 
     def __repr__(self):
         return "HistogramEqualization (num_bins=%s)" % (self._num_bins)
@@ -111,9 +121,9 @@ class TanTriggsPreprocessing(_DevicePreprocessing):
         self._sigma0 = float(sigma0)
         self._sigma1 = float(sigma1)
 
-    def _run(self, imgs_u8):
+    def _run(self, imgs):
         from .. import _device
-        return _device.tantriggs(imgs_u8, self._alpha, self._tau, self._gamma, self._sigma0, self._sigma1)
+        return _device.tantriggs(imgs, self._alpha, self._tau, self._gamma, self._sigma0, self._sigma1)
 
     def __repr__(self):
         return "TanTriggsPreprocessing (alpha=%.3f,tau=%.3f,gamma=%.3f,sigma0=%.3f,sigma1=%.3f)" % (
