@@ -481,6 +481,34 @@ int ofr_lpq_codes_f(void* stream, const void* imgs, int pixel_bytes, int64_t n, 
 int ofr_lpq_hist_f(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W, int radius,
                    const double* V_host, int gr, int gc, void* counts, int count_bytes);
 
+/* VarLBP and its density histograms (ofr_varlbp.hip) -------------------------------
+ * Replace VarLBP.__call__ lbp.py:140-208 and, under SpatialHistogram, feature.py:286-302.
+ * imgs [n][H][W] contiguous, uint8 (pixel_bytes = 1), float32 (4) or float64 (8),
+ * converted exactly to fp64; the geometry arguments are those of ofr_elbp_codes.
+ * Per code pixel, fp64 without contraction, for point i = 0..P-1:
+ *   N = w1*X; N += w2*X; N += w3*X; N += w4*X (zero weights dropped);
+ *   delta = N - mean; mean = mean + delta / (i+1); m2 = m2 + delta * (N - mean);
+ * value = m2 / (P-1), IEEE divisions: bit-equal to the reference under numpy 2.x.
+ * ofr_varlbp_values: values fp64 [n][dy][dx]; 2 <= P <= 32.
+ * ofr_varlbp_hist: np.histogram(v, bins=2^P, range=(0, 2^P)) of every cell (cells cut
+ * as for ofr_elbp_hist_geom): v counts when 0 <= v <= 2^P, in bin min((int)v, 2^P - 1);
+ * everything else, NaN included, is dropped.  counts [n][gr*gc][2^P] of count_bytes
+ * (1, 2 or 4) unsigned integers, totals int32 [n][gr*gc] = each cell's in-range count,
+ * both 4-byte aligned.  The reference's density histogram of a cell is count / total
+ * (0/0 = NaN for a cell with nothing in range).  2 <= P <= 15.
+ * P < 2 (m2 / 0) and P above the limit are OFR_E_UNSUPPORTED.
+ * ofr_hist_density_f32: counts [n][cells][bins] + totals [n][cells] -> fp32 [n][ld],
+ * ld = cells*bins rounded up to 4 (anything else is OFR_E_INVALID), out 16-byte
+ * aligned: (float)((double)count / (double)total), padding columns zero.         */
+int ofr_varlbp_values(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W, int P,
+                      const int32_t* offs_host, const double* w_host, int oy, int ox, int by, int bx,
+                      double* values);
+int ofr_varlbp_hist(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W, int P,
+                    const int32_t* offs_host, const double* w_host, int oy, int ox, int by, int bx,
+                    int gr, int gc, void* counts, int count_bytes, int32_t* totals);
+int ofr_hist_density_f32(void* stream, const void* counts, int count_bytes, const int32_t* totals,
+                         int64_t n, int cells, int bins, float* out, int64_t ld);
+
 /* Illumination normalisation (reference preprocessing.py) --------------------
  * imgs: uint8 [n][H][W] contiguous.
  * ofr_tantriggs_f32 (preprocessing.py:98-105): X = v^gamma (256-entry table,

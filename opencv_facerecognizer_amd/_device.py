@@ -1398,6 +1398,52 @@ def lpq_hist(imgs_u8, radius, V, grid, count_bytes=None):
     return out, cell, count_bytes
 
 
+def _geom_args(geom):
+    (oy, ox), (by, bx), offs, wts = geom
+    offs32 = np.ascontiguousarray(offs, dtype=np.int32)
+    w64 = np.ascontiguousarray(wts, dtype=np.float64)
+    # (the two arrays ride along so that they outlive the call)
+    return (len(offs32), offs32.ctypes.data_as(_lib.c_vp), w64.ctypes.data_as(_lib.c_vp), oy, ox, by, bx), (offs32, w64)
+
+
+def varlbp_values(imgs, geom):
+    """VarLBP (lbp.py:140-208): uint8, float32 or float64 [n][H][W] device tensor -> float64 variances
+    [n][dy][dx], bit-equal to the reference."""
+    args, keep = _geom_args(geom)
+    by, bx = args[-2:]
+    n, H, W = imgs.shape
+    out = torch.empty((n, max(H - by + 1, 0), max(W - bx + 1, 0)), dtype=torch.float64, device=imgs.device)
+    call("ofr_varlbp_values", stream(), ptr(imgs), _pixel_bytes(imgs) or 1, n, H, W, *args, ptr(out))
+    return out
+
+
+def varlbp_hist(imgs, geom, grid, count_bytes=None):
+    """-> (counts [n][gr*gc][2^P] as elbp_hist, int32 totals [n][gr*gc] = each cell's in-range count, bytes
+    per count).  The reference's histogram of a cell is counts / total (np.histogram density over
+    range=(0, 2^P)): every cell has its own denominator, 0/0 where nothing is in range."""
+    args, keep = _geom_args(geom)
+    P, (by, bx) = args[0], args[-2:]
+    n, H, W = imgs.shape
+    gr, gc = grid
+    cell = (max(H - by + 1, 0) // gr) * (max(W - bx + 1, 0) // gc)
+    count_bytes, tdt = _count_bytes(cell, count_bytes)
+    out = torch.empty((n, gr * gc, 1 << min(P, 15)), dtype=tdt, device=imgs.device)
+    totals = torch.empty((n, gr * gc), dtype=torch.int32, device=imgs.device)
+    call("ofr_varlbp_hist", stream(), ptr(imgs), _pixel_bytes(imgs) or 1, n, H, W, *args, gr, gc, ptr(out),
+         count_bytes, ptr(totals))
+    return out, totals, count_bytes
+
+
+def hist_density(counts, totals, count_bytes):
+    """counts [n][cells][bins] + totals [n][cells] -> fp32 device rows [n][ld] = (float)(count / total),
+    ld = cells * bins rounded up to 4, padding zero: the rows a Chi2Gallery(dtype=DT_F32) holds."""
+    n, cells, bins = counts.shape
+    ld = round_up(cells * bins, 4)
+    out = torch.empty((n, ld), dtype=torch.float32, device=counts.device)
+    call("ofr_hist_density_f32", stream(), ptr(counts), count_bytes, ptr(totals), n, cells, bins, ptr(out), ld)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # preprocessing  (preprocessing.py:73-77, 98-105)
 # ---------------------------------------------------------------------------

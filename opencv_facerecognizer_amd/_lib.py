@@ -133,6 +133,11 @@ SIGNATURES = {
     "ofr_olbp_hist_f": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_int, c_vp, c_int]),
     "ofr_lpq_codes_f": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_vp, c_vp]),
     "ofr_lpq_hist_f": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_int]),
+    "ofr_varlbp_values": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int,
+                                  c_int, c_vp]),
+    "ofr_varlbp_hist": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int,
+                                c_int, c_int, c_vp, c_int, c_vp]),
+    "ofr_hist_density_f32": (c_int, [c_vp, c_vp, c_int, c_vp, c_i64, c_int, c_int, c_vp, c_i64]),
     "ofr_tantriggs_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_dbl, c_dbl]),
     "ofr_tantriggs_f32": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_vp,
                                   c_sz]),

@@ -258,6 +258,33 @@ class NearestNeighbor(AbstractClassifier):
             self.__dict__["_chi2_denom"] = float(cell)
             self.__dict__["_dev"] = ((mid, id(self.X), _lib.device()), len(self.X), g)
 
+    def adopt_device_hist(self, F, nbins):
+        """Seed the fp32 histogram gallery from device rows F [N][ld] whose first nbins columns are
+        float32(self.X) (SpatialHistogram.compute with a VarLBP operator: count / total per cell, no common
+        denominator, so not a counts gallery): no float64 upload."""
+        mid = self._metric()
+        if mid not in _lib.HIST_METRICS or int(F.shape[0]) != len(self.X) or self._shard_info() is not None:
+            return
+        with _DEVICE_LOCK:
+            g = Chi2Gallery(F, dtype=_lib.DT_F32, nbins=int(nbins), metric=mid)
+            self.__dict__["_dev"] = ((mid, id(self.X), _lib.device()), len(self.X), g)
+
+    def search_density(self, F, k=None):
+        """Histogram queries as fp32 device rows F [B][nbins] (SpatialHistogram.density_batch) against the fp32
+        gallery; a counts gallery answers through its fp32 twin.  -> (distances, indices) device."""
+        k = int(self.k if k is None else k)
+        nbins = int(F.shape[1])
+        g = self._gallery()
+        B = int(F.shape[0])
+        if B and len(self.X) and nbins != g.nbins:
+            raise ValueError(f"query dimension {nbins} does not match the gallery")
+        if not (isinstance(g, Chi2Gallery) and B and g.N):
+            d, i = self.search(F.cpu().numpy().astype(np.float64), k)
+            return torch.from_numpy(d), torch.from_numpy(i)
+        if g.dtype != _lib.DT_F32:
+            g = self._float_twin()
+        return self._search_device(F.contiguous(), k, g)
+
     def search_counts(self, C, cell, count_bytes, k=None):
         """LBPH queries as device counts C [B][nbins] of `cell`-pixel cells (SpatialHistogram.counts_batch):
         the counts go straight to a counts gallery of the same cell size; otherwise (a float gallery,

@@ -563,7 +563,7 @@ class Fisherfaces(_DeviceProjMixin, AbstractFeature):
         return "Fisherfaces (num_components=%s)" % (self.num_components)
 
 
-from .lbp import LPQ, ExtendedLBP, LocalDescriptor, OriginalLBP  # noqa: E402  (feature.py:263)
+from .lbp import LPQ, ExtendedLBP, LocalDescriptor, OriginalLBP, VarLBP  # noqa: E402  (feature.py:263)
 
 
 class SpatialHistogram(AbstractFeature):
@@ -575,6 +575,12 @@ class SpatialHistogram(AbstractFeature):
     (feature.py:298-299).  ``compute`` leaves the device counts for the classifier
     (``PredictableModel.compute``): the LBPH gallery stays resident as counts, never rebuilt from
     the float64 list.
+
+    A ``VarLBP`` operator gives real variances, many of them outside ``range=(0, 2^P)``, and numpy's
+    density then divides each cell by its own in-range count: ``ofr_varlbp_hist`` returns the counts and
+    the int32 totals per cell, the float64 histograms are counts / totals (NaN for a cell with nothing in
+    range, as in the reference), and the classifier's gallery and the query batches are the fp32 rows of
+    ``density_batch`` instead of counts.
 
     Images: 8-bit grey images, or float32 / float64 images of arbitrary values (the float kernels, see
     lbp.py) -- host lists and arrays, or uint8 / float32 / float64 device tensors [n][H][W] such as
@@ -604,15 +610,19 @@ class SpatialHistogram(AbstractFeature):
 
     def counts_device(self, imgs):
         """Image stack (n,H,W), host or device, uint8 / float32 / float64 -> (counts device tensor
-        [n][cells][2^P], cell pixels, bytes)."""
+        [n][cells][2^P], cell pixels, bytes).  For a VarLBP operator the denominator is per cell: the
+        middle item is the int32 device tensor [n][cells] of in-range totals."""
         op = self.lbp_operator
-        if not isinstance(op, (ExtendedLBP, OriginalLBP, LPQ)):
-            raise NotImplementedError("SpatialHistogram (MI355X build) runs ExtendedLBP, OriginalLBP and LPQ operators only")
+        if not isinstance(op, (ExtendedLBP, OriginalLBP, LPQ, VarLBP)):
+            raise NotImplementedError("SpatialHistogram (MI355X build) runs ExtendedLBP, OriginalLBP, LPQ and VarLBP "
+                                      "operators only")
         from .lbp import as_pixel_images
         if not hasattr(imgs, "device"):
             imgs = as_pixel_images(np.ascontiguousarray(imgs) if isinstance(imgs, np.ndarray) and imgs.ndim == 3
                                    else np.stack([np.asarray(x) for x in imgs]))
         imgs = _device.pixel_images(imgs)
+        if isinstance(op, VarLBP):
+            return _device.varlbp_hist(imgs, op.geometry(), tuple(self.sz))
         if isinstance(op, LPQ):
             return _device.lpq_hist(imgs, int(op.radius), op.basis(), tuple(self.sz))
         if isinstance(op, OriginalLBP):
@@ -623,9 +633,23 @@ class SpatialHistogram(AbstractFeature):
         """Faces of one size (list, array [n][H][W] or a uint8 / float32 / float64 device tensor such as
         ``ingest.faces`` or ``preprocessing.extract_batch`` returns) -> (counts [n][cells * 2^P] device
         tensor, cell pixel count, bytes per count), one launch.  The histogram of face i is counts[i] / cell."""
+        if isinstance(self.lbp_operator, VarLBP):
+            raise NotImplementedError("VarLBP histograms have one denominator per cell, not a common one: use "
+                                      "density_batch(X) (fp32 device rows)")
         counts, cell, cb = self.counts_device(X if hasattr(X, "device") or (isinstance(X, np.ndarray) and X.ndim == 3)
                                               else list(X))
         return counts.reshape(counts.shape[0], -1), cell, cb
+
+    def density_batch(self, X):
+        """Faces of one size (as ``counts_batch`` takes them) -> fp32 device rows [n][ld] of the histograms,
+        ld = cells * 2^P: the histogram launch plus ``ofr_hist_density_f32``, each value (float)(count / total)
+        with the cell's own in-range total.  For VarLBP; the other operators' histograms are ``counts_batch``'s
+        counts / cell."""
+        if not isinstance(self.lbp_operator, VarLBP):
+            raise NotImplementedError("density_batch serves VarLBP operators; use counts_batch(X)")
+        counts, totals, cb = self.counts_device(X if hasattr(X, "device") or (isinstance(X, np.ndarray) and X.ndim == 3)
+                                               else list(X))
+        return _device.hist_density(counts, totals, cb)
 
     def histograms(self, X):
         """List of images -> list of float64 histograms = count/(py*px) (np.histogram density, :298-299)."""
@@ -641,12 +665,16 @@ class SpatialHistogram(AbstractFeature):
         for shp in shapes:   # images of one size per launch
             sel = list(range(len(X))) if on_device else [i for i, x in enumerate(X) if np.asarray(x).shape == shp]
             counts, cell, cb = self.counts_device(X if on_device else [X[i] for i in sel])
-            c = _device.counts_numpy(counts, cb).astype(np.int64).reshape(len(sel), -1)
+            c = _device.counts_numpy(counts, cb).astype(np.int64)
+            # VarLBP: one denominator per cell, the in-range totals [n][cells]
+            denom = cell.cpu().numpy().astype(np.float64)[:, :, None] if hasattr(cell, "device") else float(cell)
             with np.errstate(invalid="ignore", divide="ignore"):
-                h = c.astype(np.float64) / float(cell)
+                h = (c.astype(np.float64) / denom).reshape(len(sel), -1)
             for j, i in enumerate(sel):
                 out[i] = h[j]
-            if keep_device and len(shapes) == 1 and cell > 0:
+            if keep_device and len(shapes) == 1 and hasattr(cell, "device"):
+                dev = ("hist", _device.hist_density(counts, cell, cb), int(h.shape[1]))
+            elif keep_device and len(shapes) == 1 and cell > 0:
                 dev = ("counts", counts.reshape(len(sel), -1), cell, cb)
         return out, dev
 

@@ -30,8 +30,12 @@ has centres near 255.  OriginalLBP compares the values as given.  Codes touching
 a non-finite pixel (a constant face under Tan-Triggs is 0/0) are unspecified;
 they stay inside the histogram range.
 
-Out of scope: VarLBP (lbp.py:140-208) — its values are real variances that
-mostly fall outside the histogram range.
+``VarLBP`` (lbp.py:140-208) keeps its constructor, ``repr`` and pickled state
+too.  ``__call__`` returns the float64 variance image of the ``ofr_varlbp_values``
+kernel (ofr_varlbp.hip): ExtendedLBP's geometry, the reference's Welford
+recurrence over the circle in float64 with IEEE divisions, bit for bit.  Its
+values are real variances and many fall outside the histogram range, so under
+``SpatialHistogram`` every cell has its own denominator.
 """
 from __future__ import annotations
 
@@ -141,6 +145,33 @@ class ExtendedLBP(LocalDescriptor):
         return "ExtendedLBP (neighbors=%s, radius=%s)" % (self._neighbors, self._radius)
 
 
+class VarLBP(LocalDescriptor):
+    """lbp.py:140-208 on the GPU: the variance of the circle's samples, float64 [dy][dx]."""
+
+    def __init__(self, radius=1, neighbors=8):
+        LocalDescriptor.__init__(self, neighbors=neighbors)
+        self._radius = radius
+
+    def geometry(self):
+        return elbp_geometry(self._radius, self._neighbors)
+
+    def __call__(self, X):
+        from .. import _device
+        return _device.varlbp_values(_device_image(X, "VarLBP"), self.geometry()).cpu().numpy()[0]
+
+    def values_batch(self, imgs_device):
+        """uint8, float32 or float64 [n][H][W] device tensor -> float64 variances [n][dy][dx] (device)."""
+        from .. import _device
+        return _device.varlbp_values(_device.pixel_images(imgs_device), self.geometry())
+
+    @property
+    def radius(self):
+        return self._radius
+
+    def __repr__(self):
+        return "VarLBP (neighbors=%s, radius=%s)" % (self._neighbors, self._radius)
+
+
 class OriginalLBP(LocalDescriptor):
     """lbp.py:55-72 on the GPU: the 3x3 operator, codes [H-2][W-2]."""
 
@@ -226,5 +257,5 @@ class LPQ(LocalDescriptor):
         return "LPQ (neighbors=%s, radius=%s)" % (self._neighbors, self._radius)
 
 
-for _c in (LocalDescriptor, ExtendedLBP, OriginalLBP, LPQ):
+for _c in (LocalDescriptor, ExtendedLBP, VarLBP, OriginalLBP, LPQ):
     _c.__module__ = "ocvfacerec.facerec.lbp"

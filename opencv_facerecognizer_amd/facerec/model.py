@@ -15,7 +15,9 @@ features never leave the GPU:
   preprocessing chained in front (``ChainOperator``; TanTriggsPreprocessing, HistogramEqualization or
   a ChainOperator of them at any depth): one launch per preprocessing step, whose float faces go to
   the next step's float kernel and to the float histogram kernels (``ofr_*_hist_f``) on the device,
-  then the counts search;
+  then the counts search.  A ``VarLBP`` operator has one denominator per cell, so its route carries fp32
+  rows instead of counts: ``ofr_varlbp_hist`` + ``ofr_hist_density_f32`` per batch, searched against the
+  fp32 gallery ``compute`` left on the device;
 * ChainOperator(preprocessing as above, Fisherfaces) + NearestNeighbor (Euclidean/Cosine): the
   preprocessing launches (``ofr_tantriggs_f32`` / ``ofr_histeq_f64`` and their ``_f`` twins for
   float faces), one fp64 projection with the gallery centring folded in, one search.
@@ -27,7 +29,7 @@ import numpy as np
 from .. import _lib
 from .classifier import AbstractClassifier, NearestNeighbor, results
 from .feature import AbstractFeature, Fisherfaces, SpatialHistogram
-from .lbp import LPQ, ExtendedLBP, OriginalLBP
+from .lbp import LPQ, ExtendedLBP, OriginalLBP, VarLBP
 from .operators import ChainOperator
 from .preprocessing import HistogramEqualization, TanTriggsPreprocessing
 
@@ -42,6 +44,17 @@ def _preprocessing(f):
 def _preprocessed(f):
     """ChainOperator(preprocessing, feature): the device routes run model1's launches in front of model2."""
     return type(f) is ChainOperator and _preprocessing(f.model1)
+
+
+def _size_groups(X):
+    """Faces -> (X as a list or one-size batch, [(positions or None, faces of one size)])."""
+    if hasattr(X, "device") or (isinstance(X, np.ndarray) and X.ndim == 3):   # one face size
+        return X, [(None, X)]
+    X = list(X)
+    shapes = {}
+    for i, x in enumerate(X):
+        shapes.setdefault(np.asarray(x).shape, []).append(i)
+    return X, [(sel, [X[i] for i in sel]) for sel in shapes.values()]
 
 
 class PredictableModel(object):
@@ -66,6 +79,9 @@ class PredictableModel(object):
             if hasattr(self.classifier, "adopt_device_counts"):
                 _, C, cell, cb = dev[1]
                 self.classifier.adopt_device_counts(C, cell, cb)
+        elif isinstance(dev[1], tuple) and dev[1][0] == "hist":       # SpatialHistogram(VarLBP) fp32 rows
+            if hasattr(self.classifier, "adopt_device_hist"):
+                self.classifier.adopt_device_hist(dev[1][1], dev[1][2])
         elif hasattr(self.classifier, "adopt_device_rows"):
             self.classifier.adopt_device_rows(dev[1])
 
@@ -77,7 +93,8 @@ class PredictableModel(object):
 
     def predict(self, X):
         """model.py:53-55 (one face)."""
-        if self._chain() or self._lbph_chain():     # one face: the reference's own order, extract then classify
+        # one face: the reference's own order, extract then classify
+        if self._chain() or self._lbph_chain() or self._varlbp():
             return self.classifier.predict(self.feature.extract(X))
         return self.predict_batch([X])[0]
 
@@ -107,9 +124,13 @@ class PredictableModel(object):
         f = self.feature
         if _preprocessed(f):
             f = f.model2
-        return (type(f) is SpatialHistogram and isinstance(f.lbp_operator, (ExtendedLBP, OriginalLBP, LPQ))
+        return (type(f) is SpatialHistogram and isinstance(f.lbp_operator, (ExtendedLBP, OriginalLBP, LPQ, VarLBP))
                 and type(self.classifier) is NearestNeighbor
                 and getattr(self.classifier.dist_metric, "metric_id", None) in _lib.HIST_METRICS)
+
+    def _varlbp(self):
+        f = self.feature.model2 if _preprocessed(self.feature) else self.feature
+        return self._lbph() and isinstance(f.lbp_operator, VarLBP)
 
     def _search_device(self, X, k=None):
         clf = self.classifier
@@ -129,8 +150,11 @@ class PredictableModel(object):
 
     def _search_lbph(self, X, k):
         """LBPH batch: faces grouped by size, one histogram launch + one counts search per group (behind a
-        preprocessing step: its launch first, the float faces stay on the device)."""
+        preprocessing step: its launch first, the float faces stay on the device).  VarLBP: one histogram
+        and one density launch per group, then one search of all the fp32 rows."""
         import torch
+        if self._varlbp():
+            return self._search_varlbp(X, k)
         if self._lbph_chain():
             pre, sh = self.feature.model1, self.feature.model2
 
@@ -138,14 +162,7 @@ class PredictableModel(object):
                 return sh.counts_batch(pre.extract_batch(xs))
         else:
             counts_batch = self.feature.counts_batch
-        if hasattr(X, "device") or (isinstance(X, np.ndarray) and X.ndim == 3):   # one face size
-            groups = [(None, X)]
-        else:
-            X = list(X)
-            shapes = {}
-            for i, x in enumerate(X):
-                shapes.setdefault(np.asarray(x).shape, []).append(i)
-            groups = [(sel, [X[i] for i in sel]) for sel in shapes.values()]
+        X, groups = _size_groups(X)
         if len(groups) == 1:
             C, cell, cb = counts_batch(groups[0][1])
             return self.classifier.search_counts(C, cell, cb, k)
@@ -164,6 +181,20 @@ class PredictableModel(object):
             d_all.index_copy_(0, idx, d.to(dev, d_all.dtype))
             i_all.index_copy_(0, idx, i.to(dev, i_all.dtype))
         return d_all, i_all
+
+    def _search_varlbp(self, X, k):
+        import torch
+        sh = self.feature.model2 if self._lbph_chain() else self.feature
+        pre = self.feature.model1 if self._lbph_chain() else None
+        X, groups = _size_groups(X)
+        rows = [sh.density_batch(pre.extract_batch(xs) if pre is not None else xs) for _, xs in groups]
+        if len(groups) == 1:
+            return self.classifier.search_density(rows[0], k)
+        # every size gives rows of the same width (cells * 2^P): back into the callers' order, one search
+        F = torch.empty((len(X), rows[0].shape[1]), dtype=rows[0].dtype, device=rows[0].device)
+        for (sel, _), r in zip(groups, rows):
+            F.index_copy_(0, torch.tensor(sel, dtype=torch.int64, device=F.device), r)
+        return self.classifier.search_density(F, k)
 
     def predict_batch(self, X):
         """Predict a batch of faces (list of 2-D arrays, an array [B, H, W], or a uint8 device
