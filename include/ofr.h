@@ -509,6 +509,24 @@ int ofr_varlbp_hist(void* stream, const void* imgs, int pixel_bytes, int64_t n, 
 int ofr_hist_density_f32(void* stream, const void* counts, int count_bytes, const int32_t* totals,
                          int64_t n, int cells, int bins, float* out, int64_t ld);
 
+/* Multi-scale LBP histograms (ofr_mslbp.hip) ---------------------------------------
+ * The feature rows of CombineOperator(SpatialHistogram(ExtendedLBP(r_0, P), sz), ...) with
+ * S = 2..4 scales that share P (2..8) and the grid gr x gc, in one launch.
+ * imgs [n][H][W] contiguous, uint8 (pixel_bytes = 1), float32 (4) or float64 (8).
+ * Geometry per scale s, as ofr_elbp_codes takes it: offs [S][P][4], w [S][P][4] and
+ * block [S][4] = oy, ox, by, bx.  Codes are those of ofr_elbp_hist_geom (uint8) and
+ * ofr_elbp_hist_f (float), bit for bit; cells are cut per scale as there
+ * (py_s = dy_s / gr, px_s = dx_s / gc).
+ * counts (or NULL): uint16 [n][S][gr*gc][2^P], 4-byte aligned.
+ * rows (or NULL): fp32 [n][ld], 16-byte aligned, ld a multiple of 4 >= S*gr*gc*2^P:
+ * scale-major, cells row-major, bins; (float)((double)count / (double)(py_s*px_s)),
+ * padding columns zero.  At least one of the two.
+ * OFR_E_UNSUPPORTED: S or P outside their ranges, a scale whose cell holds no or more
+ * than 65535 code pixels, one cell row of all scales above the 160 KiB of LDS.        */
+int ofr_mslbp_hist(void* stream, const void* imgs, int pixel_bytes, int64_t n, int H, int W, int S, int P,
+                   const int32_t* offs, const double* w, const int32_t* block, int gr, int gc,
+                   uint16_t* counts, float* rows, int64_t ld);
+
 /* Illumination normalisation (reference preprocessing.py) --------------------
  * imgs: uint8 [n][H][W] contiguous.
  * ofr_tantriggs_f32 (preprocessing.py:98-105): X = v^gamma (256-entry table,

@@ -1444,6 +1444,26 @@ def hist_density(counts, totals, count_bytes):
     return out
 
 
+def mslbp_hist(imgs, geoms, grid, counts=True, rows=True, ld=None):
+    """Multi-scale LBP histograms, one launch: imgs uint8 / float32 / float64 [n][H][W] device tensor, geoms the
+    S scales' ExtendedLBP geometries (one P) -> (counts int16-stored uint16 [n][S][gr*gc][2^P] or None, fp32
+    rows [n][ld] or None, [cell pixel count per scale]); ld defaults to the row length S*gr*gc*2^P."""
+    n, H, W = imgs.shape
+    gr, gc = grid
+    S, P = len(geoms), len(geoms[0][2])
+    offs = np.ascontiguousarray([g[2] for g in geoms], dtype=np.int32)
+    wts = np.ascontiguousarray([g[3] for g in geoms], dtype=np.float64)
+    block = np.ascontiguousarray([tuple(g[0]) + tuple(g[1]) for g in geoms], dtype=np.int32)
+    cells = [(max(H - by + 1, 0) // gr) * (max(W - bx + 1, 0) // gc) for _, (by, bx), _, _ in geoms]
+    width = S * gr * gc * (1 << P)
+    C = torch.empty((n, S, gr * gc, 1 << P), dtype=torch.int16, device=imgs.device) if counts else None
+    R = torch.empty((n, width if ld is None else ld), dtype=torch.float32, device=imgs.device) if rows else None
+    call("ofr_mslbp_hist", stream(), ptr(imgs), _pixel_bytes(imgs) or 1, n, H, W, S, P, offs.ctypes.data_as(_lib.c_vp),
+         wts.ctypes.data_as(_lib.c_vp), block.ctypes.data_as(_lib.c_vp), gr, gc, ptr(C), ptr(R),
+         0 if R is None else R.shape[1])
+    return C, R, cells
+
+
 # ---------------------------------------------------------------------------
 # preprocessing  (preprocessing.py:73-77, 98-105)
 # ---------------------------------------------------------------------------

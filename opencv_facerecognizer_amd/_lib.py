@@ -138,6 +138,8 @@ SIGNATURES = {
     "ofr_varlbp_hist": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int,
                                 c_int, c_int, c_vp, c_int, c_vp]),
     "ofr_hist_density_f32": (c_int, [c_vp, c_vp, c_int, c_vp, c_i64, c_int, c_int, c_vp, c_i64]),
+    "ofr_mslbp_hist": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
+                               c_vp, c_vp, c_i64]),
     "ofr_tantriggs_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_dbl, c_dbl]),
     "ofr_tantriggs_f32": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_vp,
                                   c_sz]),

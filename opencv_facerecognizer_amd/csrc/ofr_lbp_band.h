@@ -11,6 +11,14 @@ constexpr int THREADS = 1024;
 constexpr int LDS_MAX = 160 * 1024;
 constexpr int LDS_HALF = 80 * 1024;  // two workgroups per CU
 
+// np.asarray(x, dtype=np.uint8) of a float as fp64: (int64)trunc(x) & 255
+__device__ __forceinline__ double centre_u8(double x) {
+  const double t = trunc(x);
+  const double q = floor(t * 0.00390625);
+  const double m = 256.0 * q;
+  return t - m;
+}
+
 // `count` contiguous pixels (uint8, float32 or float64) -> fp64 in LDS: 16-byte loads from the first
 // 16-byte boundary on, the elements in front of it and behind the last whole vector one by one
 template <typename T>

@@ -71,14 +71,6 @@ struct Band {
   int coff;         // centre offset oy*W + ox
 };
 
-// np.asarray(x, dtype=np.uint8) of a float as fp64: (int64)trunc(x) & 255
-__device__ __forceinline__ double centre_u8(double x) {
-  const double t = trunc(x);
-  const double q = floor(t * 0.00390625);
-  const double m = 256.0 * q;
-  return t - m;
-}
-
 template <int FORM>
 __global__ void __launch_bounds__(THREADS) band_hist_kernel(const void* __restrict__ imgs, LbpGeom g, Band a, R1P8 k,
                                                             void* __restrict__ counts) {

@@ -17,7 +17,13 @@ features never leave the GPU:
   the next step's float kernel and to the float histogram kernels (``ofr_*_hist_f``) on the device,
   then the counts search.  A ``VarLBP`` operator has one denominator per cell, so its route carries fp32
   rows instead of counts: ``ofr_varlbp_hist`` + ``ofr_hist_density_f32`` per batch, searched against the
-  fp32 gallery ``compute`` left on the device;
+  fp32 gallery ``compute`` left on the device.  A multi-scale LBP histogram,
+  ``CombineOperator(SpatialHistogram(ExtendedLBP(r, P), sz), ...)`` of 2..4 scales (``operators.fused_scales``),
+  bare or behind preprocessing, carries fp32 rows too: ONE ``ofr_mslbp_hist`` launch per batch gives the
+  rows of all scales, searched against the fp32 gallery ``compute`` left on the device.  The route is chosen
+  by the tree alone: faces of a size the kernel does not take (``fused_scales`` is None for it) still go this
+  way, and ``CombineOperator.density_batch`` then builds their rows from the members' own kernels on the host
+  and uploads them -- correct, but a host round trip per batch;
 * ChainOperator(preprocessing as above, Fisherfaces) + NearestNeighbor (Euclidean/Cosine): the
   preprocessing launches (``ofr_tantriggs_f32`` / ``ofr_histeq_f64`` and their ``_f`` twins for
   float faces), one fp64 projection with the gallery centring folded in, one search.
@@ -30,7 +36,7 @@ from .. import _lib
 from .classifier import AbstractClassifier, NearestNeighbor, results
 from .feature import AbstractFeature, Fisherfaces, SpatialHistogram
 from .lbp import LPQ, ExtendedLBP, OriginalLBP, VarLBP
-from .operators import ChainOperator
+from .operators import ChainOperator, CombineOperator
 from .preprocessing import HistogramEqualization, TanTriggsPreprocessing
 
 
@@ -71,7 +77,8 @@ class PredictableModel(object):
         builds its device gallery from them (no host round trip of the gallery)."""
         features = self.feature.compute(X, y)
         self.classifier.compute(features, y)
-        holder = self.feature.model2 if self._lbph_chain() else self.feature   # who left device features
+        chained = self._lbph_chain() or (self._mslbp() and _preprocessed(self.feature))
+        holder = self.feature.model2 if chained else self.feature   # who left device features
         dev = holder.__dict__.pop("_dev_features", None)
         if dev is None or dev[0] != id(features):
             return
@@ -79,7 +86,7 @@ class PredictableModel(object):
             if hasattr(self.classifier, "adopt_device_counts"):
                 _, C, cell, cb = dev[1]
                 self.classifier.adopt_device_counts(C, cell, cb)
-        elif isinstance(dev[1], tuple) and dev[1][0] == "hist":       # SpatialHistogram(VarLBP) fp32 rows
+        elif isinstance(dev[1], tuple) and dev[1][0] == "hist":       # fp32 rows: VarLBP, multi-scale LBP
             if hasattr(self.classifier, "adopt_device_hist"):
                 self.classifier.adopt_device_hist(dev[1][1], dev[1][2])
         elif hasattr(self.classifier, "adopt_device_rows"):
@@ -94,7 +101,7 @@ class PredictableModel(object):
     def predict(self, X):
         """model.py:53-55 (one face)."""
         # one face: the reference's own order, extract then classify
-        if self._chain() or self._lbph_chain() or self._varlbp():
+        if self._chain() or self._lbph_chain() or self._varlbp() or self._mslbp():
             return self.classifier.predict(self.feature.extract(X))
         return self.predict_batch([X])[0]
 
@@ -132,11 +139,20 @@ class PredictableModel(object):
         f = self.feature.model2 if _preprocessed(self.feature) else self.feature
         return self._lbph() and isinstance(f.lbp_operator, VarLBP)
 
+    def _mslbp(self):
+        """A multi-scale LBP histogram (a CombineOperator that takes device batches), bare or behind
+        preprocessing, searched with a histogram metric."""
+        f = self.feature.model2 if _preprocessed(self.feature) else self.feature
+        return (type(f) is CombineOperator and f.device_batches and type(self.classifier) is NearestNeighbor
+                and getattr(self.classifier.dist_metric, "metric_id", None) in _lib.HIST_METRICS)
+
     def _search_device(self, X, k=None):
         clf = self.classifier
         k = int(clf.k if k is None else k)
         if self._lbph():
             return self._search_lbph(X, k)
+        if self._mslbp():
+            return self._search_density(X, k)
         g = clf._gallery()
         proj = self.feature
         if self._chain():     # illumination normalisation on the device, its float faces go to the fp64 GEMM
@@ -154,7 +170,7 @@ class PredictableModel(object):
         and one density launch per group, then one search of all the fp32 rows."""
         import torch
         if self._varlbp():
-            return self._search_varlbp(X, k)
+            return self._search_density(X, k)
         if self._lbph_chain():
             pre, sh = self.feature.model1, self.feature.model2
 
@@ -182,10 +198,13 @@ class PredictableModel(object):
             i_all.index_copy_(0, idx, i.to(dev, i_all.dtype))
         return d_all, i_all
 
-    def _search_varlbp(self, X, k):
+    def _search_density(self, X, k):
+        """VarLBP and multi-scale LBP: the preprocessing launches, one ``density_batch`` per face size, one search
+        of all the fp32 rows."""
         import torch
-        sh = self.feature.model2 if self._lbph_chain() else self.feature
-        pre = self.feature.model1 if self._lbph_chain() else None
+        chained = _preprocessed(self.feature)
+        sh = self.feature.model2 if chained else self.feature
+        pre = self.feature.model1 if chained else None
         X, groups = _size_groups(X)
         rows = [sh.density_batch(pre.extract_batch(xs) if pre is not None else xs) for _, xs in groups]
         if len(groups) == 1:
@@ -199,7 +218,7 @@ class PredictableModel(object):
     def predict_batch(self, X):
         """Predict a batch of faces (list of 2-D arrays, an array [B, H, W], or a uint8 device
         tensor [B, H, W] such as ``ingest.faces`` returns)."""
-        if not (self._fused() or self._lbph() or self._chain()):
+        if not (self._fused() or self._lbph() or self._chain() or self._mslbp()):
             if hasattr(X, "data_ptr"):   # a device face batch: the generic path works on host items
                 X = list(X.cpu().numpy())
             qs = [self.feature.extract(x) for x in X]
